@@ -2,12 +2,17 @@
 """Benchmark: pods scheduled/sec for Solve on BASELINE.json configs[1] (50k heterogeneous pods × the 918-type
 EC2 catalog × 3 AZ × {spot, on-demand}) on the gfx950 library.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One step = one kp_solve_execute (queue sort, class×type masks, template filter, the FFD Solve kernel and
 Truncate(60)) with every input already resident in HBM.  Provisioning Solve is a serial chain, so N GPUs run
 N independent replicas ("replicas only"); value = pods of all ranks ÷ max-over-ranks time.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR also fetches the last timed
+step's result and writes it to DIR/<name>.npy (the inputs are seeded, so two builds can be compared array for array).
+--full adds everything else the run can measure: the PCIe-inclusive kp_solve calls, roofline and stage-cycle figures,
+the consolidation, launch, topology and reserved legs, the CPU baselines and the parity checks against them.
 """
 import argparse
 import json
@@ -463,7 +468,15 @@ def main():
     ap.add_argument("--resv-cpu-sample", type=int, default=40_000,
                     help="pods in config5's CPU-baseline sample (the full 200k takes the oracle ~9 min: its reservation "
                          "bookkeeping grows with NodeClaims x pods; DESIGN.md §6)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline figure: the end-to-end kp_solve calls, the roofline and "
+                         "stage-cycle figures, the consolidation / launch / topology / reserved legs, the CPU baselines "
+                         "and the parity checks against them (the --no-* options choose among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's Solve result to DIR/<name>.npy (float64)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -487,23 +500,27 @@ def main():
     cap_nc = max(16, prob.pods.n + 1)
     out = model.OutputBuffers(prob.pods.n, cap_nc, cap_nc * 60)
 
-    # end-to-end (PCIe-inclusive) call once, for the record
-    t = time.perf_counter()
-    ctx.solve(iv, out)
-    e2e_ms = (time.perf_counter() - t) * 1e3
-    res = out.results()
-    cyc = ctx.ffd_cycles()
-    # the same kp_solve call again (warm: device buffers, kernel modules and the hipcub workspace exist), with its
-    # phases from kp_solve_stats: host prepare (intern + encode + upload), device execute, fetch + decode
-    e2e_warm = []
-    for _ in range(3):
+    e2e_ms = res = cyc = solve_call = None
+    if a.full:
+        # end-to-end (PCIe-inclusive) call once, for the record
         t = time.perf_counter()
         ctx.solve(iv, out)
-        e2e_warm.append((time.perf_counter() - t) * 1e3)
-    st = out.results().stats
-    solve_call = {"ms": float(np.median(e2e_warm)), "host_prep_ms": st["ns_host_prep"] / 1e6,
-                  "device_execute_ms": st["ns_device_solve"] / 1e6, "fetch_ms": st["ns_device_finalize"] / 1e6}
+        e2e_ms = (time.perf_counter() - t) * 1e3
+        res = out.results()
+        cyc = ctx.ffd_cycles()
+        # the same kp_solve call again (warm: device buffers, kernel modules and the hipcub workspace exist), with its
+        # phases from kp_solve_stats: host prepare (intern + encode + upload), device execute, fetch + decode
+        e2e_warm = []
+        for _ in range(3):
+            t = time.perf_counter()
+            ctx.solve(iv, out)
+            e2e_warm.append((time.perf_counter() - t) * 1e3)
+        st = out.results().stats
+        solve_call = {"ms": float(np.median(e2e_warm)), "host_prep_ms": st["ns_host_prep"] / 1e6,
+                      "device_execute_ms": st["ns_device_solve"] / 1e6, "fetch_ms": st["ns_device_finalize"] / 1e6}
     ctx.prepare(iv)  # inputs resident in HBM from here on
+    if not a.full:
+        ctx.execute()  # untimed, as the calls above: the first execute loads the kernel modules and sizes the workspace
 
     for _ in range(a.warmup):
         ctx.execute()
@@ -529,16 +546,70 @@ def main():
         elapsed = float(tt.item())
 
     kt = np.array(ffd_ms).mean(axis=0)
-    stages = stage_cycles_per_pod(ctx, iv, out, prob.pods.n) if rank == 0 else None
     P = prob.pods.n
     value = P * a.steps * world / elapsed
+    T = len(cat)
+    log("config2 solve leg done: %.1f ms/step" % (elapsed / a.steps * 1e3))
+    dumped = dump_outputs(a.dump_outputs, ctx, out) if a.dump_outputs and rank == 0 else None
+
+    line = {
+        "metric": "pods scheduled/sec (Solve, 50k pods × EC2 catalog)",
+        "value": value,
+        "unit": "pods/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic (seeded config2 over the reference's golden 918-type catalog)",
+        "config": {"workload": "config2: %d heterogeneous pods (250 classes) x %d types x 3 AZ x {spot,on-demand},"
+                               " 2 NodePools" % (P, T), "pods": P, "types": T,
+                   "parallelism": "replicas" if world > 1 else "single"},
+        "kernel_ms": {"queue_sort": float(kt[0]), "class_mask": float(kt[1]), "template_init": float(kt[2]),
+                      "ffd": float(kt[3]), "finalize": float(kt[4])},
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
+    if a.full:
+        line.update(full_legs(a, ctx, iv, out, prob, cat, res, cyc, e2e_ms, solve_call, kt,
+                              local, rank, world, dist, barrier))
+    if rank == 0:
+        print(json.dumps(line))
+    ctx.close()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, ctx, out):
+    """kp_solve_fetch of the last timed kp_solve_execute, written as path/<name>.npy: the arrays of kp_solve_output a
+    caller of the Solve receives (per pod: its NodeClaim and its place in the queue order; per NodeClaim: NodePool, pod
+    count, slice position, option count and its instance-type ids as offsets into type_ids).  The values are int32,
+    stored as float64 (exact)."""
+    ctx.fetch(out)
+    o, arr = out.view, out.arrays
+    n = o.n_nodeclaims
+    off = arr["nodeclaim_type_offset"][:n + 1]
+    sizes = {"nodeclaim_nodepool": n, "nodeclaim_n_pods": n, "nodeclaim_slice_pos": n, "nodeclaim_n_options": n,
+             "nodeclaim_type_offset": n + 1, "type_ids": int(off[n]), "pod_result": out.n_pods, "pod_order": out.n_pods}
+    os.makedirs(path, exist_ok=True)
+    for name, k in sizes.items():
+        np.save(os.path.join(path, name + ".npy"), arr[name][:k].astype(np.float64))
+    return {"dir": path, "nodeclaims": int(n), "arrays": sizes}
+
+
+def full_legs(a, ctx, iv, out, prob, cat, res, cyc, e2e_ms, solve_call, kt, local, rank, world, dist, barrier):
+    """--full: everything the run measures and checks besides the headline figure; returns its keys of the result line."""
+    from kpsim import model, synth
+    stages = stage_cycles_per_pod(ctx, iv, out, prob.pods.n) if rank == 0 else None
     T = len(cat)
     B = algorithmic_bytes(res.stats, res.n_nodeclaims, T)
     ffd_s = kt[3] / 1e3
     achieved = B / ffd_s / 1e9
     traffic = pmc_traffic("ffd")
 
-    log("config2 solve leg done: %.1f ms/step" % (elapsed / a.steps * 1e3))
     cons = None if (a.no_consolidation or a.no_config4) else consolidation_leg(a, cat, local, rank, world, dist, barrier)
     log("consolidation leg done")
     cons_r = None if (a.no_consolidation or a.no_consolidation_replace) else consolidation_leg(
@@ -574,48 +645,26 @@ def main():
         except AssertionError:
             parity_ok = False
 
-    if rank == 0:
-        line = {
-            "metric": "pods scheduled/sec (Solve, 50k pods × EC2 catalog)",
-            "value": value,
-            "unit": "pods/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic (seeded config2 over the reference's golden 918-type catalog)",
-            "config": {"workload": "config2: %d heterogeneous pods (250 classes) x %d types x 3 AZ x {spot,on-demand},"
-                                   " 2 NodePools" % (P, T), "pods": P, "types": T,
-                       "parallelism": "replicas" if world > 1 else "single"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": "ffd_kernel", "kernel_ms": float(kt[3]), "algorithmic_bytes": int(B),
-                         "note": ROOFLINE_NOTE},
-            "stage_cycles_per_pod": stages,
-            "cpu_baseline": cpu,
-            "parity_vs_cpu_baseline": parity_ok,  # device result bit-identical to the oracle's on the same input
-            "kernel_ms": {"queue_sort": float(kt[0]), "class_mask": float(kt[1]), "template_init": float(kt[2]),
-                          "ffd": float(kt[3]), "finalize": float(kt[4])},
-            "end_to_end_ms": e2e_ms,
-            "solve_call_warm": solve_call,
-            "ffd_counters": dict(zip(FFD_COUNTERS, cyc)),
-            "nodeclaims": res.n_nodeclaims,
-            "unschedulable": int((res.pod_result == -1).sum()),
-            "solve_stats": {k: v for k, v in res.stats.items() if not k.startswith("ns_")},
-            "consolidation": cons,
-            "consolidation_replace": cons_r,
-            "launch": launch,
-            "topology": topo,
-            "reserved": resv,
-        }
-        print(json.dumps(line))
-    ctx.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    return {
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "kernel": "ffd_kernel", "kernel_ms": float(kt[3]), "algorithmic_bytes": int(B),
+                     "note": ROOFLINE_NOTE},
+        "stage_cycles_per_pod": stages,
+        "cpu_baseline": cpu,
+        "parity_vs_cpu_baseline": parity_ok,  # device result bit-identical to the oracle's on the same input
+        "end_to_end_ms": e2e_ms,
+        "solve_call_warm": solve_call,
+        "ffd_counters": dict(zip(FFD_COUNTERS, cyc)),
+        "nodeclaims": res.n_nodeclaims,
+        "unschedulable": int((res.pod_result == -1).sum()),
+        "solve_stats": {k: v for k, v in res.stats.items() if not k.startswith("ns_")},
+        "consolidation": cons,
+        "consolidation_replace": cons_r,
+        "launch": launch,
+        "topology": topo,
+        "reserved": resv,
+    }
 
 
 if __name__ == "__main__":

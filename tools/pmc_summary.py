@@ -32,10 +32,10 @@ def counter_per_launch(d, name, kernel="ffd_kernel"):
 
 
 WAVES = {"ffd_kernel": 8, "ffd_topo_kernel": 4, "ffd_resv_kernel": 8}  # kp_layout.h KP_NWAVES / KP_NWAVES_TOPO
-MAIN_CMD = ("python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --no-consolidation-replace (config 2, config 4, "
+MAIN_CMD = ("python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --no-consolidation-replace (config 2, config 4, "
             "config 5 launch, config 3, config 5 200k Solve)")
-REPL_CMD = ("python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --no-config4 --no-launch --no-topology --no-reserved "
-            "(config 2 and the config4-replace consolidation leg)")
+REPL_CMD = ("python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --no-config4 --no-launch --no-topology "
+            "--no-reserved (config 2 and the config4-replace consolidation leg)")
 
 
 def hbm_record(out, sub, kernel, tag, command):

@@ -7,10 +7,10 @@
 set -euo pipefail
 TAG=${1:-r01}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-OUT=$ROOT/gpurun_out/prof_$TAG
+OUT=$ROOT/bench_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="$ROOT/bench.py --no-cpu-baseline --steps 3 --warmup 1"
+BENCH="$ROOT/bench.py --full --no-cpu-baseline --steps 3 --warmup 1"
 MAIN="$BENCH --no-consolidation-replace"                          # config 2, 4, launch, 3, 5
 REPL="$BENCH --no-config4 --no-launch --no-topology --no-reserved"  # config 2 + the config4-replace leg
 SOLVE="$BENCH --no-consolidation --no-launch"                     # config 2, 3, 5

@@ -4,10 +4,10 @@
 set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-r04}
-OUT=$ROOT/gpurun_out/pmc_$TAG
+OUT=$ROOT/bench_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="$ROOT/bench.py --no-cpu-baseline --no-consolidation --no-launch --no-reserved --steps 1 --warmup 0"
+BENCH="$ROOT/bench.py --full --no-cpu-baseline --no-consolidation --no-launch --no-reserved --steps 1 --warmup 0"
 timeout -s KILL 120 rocprofv3 -L > "$OUT/counters.txt" 2>&1 || true
 timeout -k 10 200 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM -T -d "$OUT/sq1" -o run --output-format csv -- python3 $BENCH > "$OUT/sq1.json" 2> "$OUT/sq1.err" || { tail -5 "$OUT/sq1.err"; exit 1; }
 timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INSTS_BRANCH -T -d "$OUT/sq2" -o run --output-format csv -- python3 $BENCH > "$OUT/sq2.json" 2> "$OUT/sq2.err" || { tail -5 "$OUT/sq2.err"; exit 1; }
