@@ -460,6 +460,7 @@ struct kp_ctx {
     double kernel_ms[5] = {};
     int64_t cycles[37] = {};  // FFD phases (s_memtime): pop, sort, scan+eval, templates, commit, full pdqsort
     bool any_min_values = false;             // some template requirement carries minValues
+    int max_min_values = 0;                  // the largest minValues among the template requirements
     bool min_multi = false;                  // ... on a multi-valued catalog key (zone, capacity type, ...)
     std::vector<uint8_t> cons_mutcls;        // per (expanded) class: its NotIn/DoesNotExist merge can change a node's
                                              // requirements in a way a later decision sees (MUT probes)
@@ -1968,6 +1969,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     c->prepared = c->executed = false;
     c->cons_prepared = false;
     c->any_min_values = false;
+    c->max_min_values = 0;
     c->min_multi = false;
     if (in->min_values_policy != KP_MIN_VALUES_STRICT && in->min_values_policy != KP_MIN_VALUES_BEST_EFFORT)
         return fail(ctx, KP_E_INVALID, "unknown MIN_VALUES_POLICY");
@@ -2224,6 +2226,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
             if (kv.second.has_min) {
                 min_keys[(size_t)j * KP_MAX_CLASS_KEYS + q++] = kv.first;
                 c->any_min_values = true;
+                c->max_min_values = std::max(c->max_min_values, (int)kv.second.minv);
                 if (kv.first < c->Kcat && (c->cat_kflags[kv.first] & KF_CAT_MULTI)) c->min_multi = true;
             }
     }
@@ -3449,6 +3452,12 @@ static kp_status cons_prepare_one(kp_ctx* ctx, const kp_consolidate_input* in) t
     // relaxed minValues, per-probe positive hostname domains, prefix-OR distinct counts)
     const KpDev& d = c->dev;
     if (d.M <= 0 || d.M > 64) return fail(ctx, KP_E_UNSUPPORTED, "consolidation needs max_instance_types in 1..64");
+    // A list of M types cannot hold minValues > M distinct values: TruncateInstanceTypes drops every NodeClaim of such a
+    // NodePool, and the probes count NodeClaims (and stop at the second) before that drop.  BestEffort relaxes minValues.
+    if (!c->best_effort && c->max_min_values > d.M)
+        return fail(ctx, KP_E_UNSUPPORTED,
+                    "consolidation with max_instance_types below a NodePool's minValues (every NodeClaim of that "
+                    "NodePool fails TruncateInstanceTypes)");
     const int T = c->T, TW = c->TW, R = c->R, A = d.n_active;
     hipStream_t s = c->stream;
     KpCons& k = c->cons;

@@ -151,7 +151,9 @@ def solve(problem, catalog_view=None, preference_policy=0, reserved_capacity=1):
     cv = catalog_view or model.CatalogView(problem.catalog)
     iv = model.SolveInputView(problem)
     cap_nc = max(16, problem.pods.n + 1)
-    ob = model.OutputBuffers(problem.pods.n, cap_nc, cap_nc * max(1, problem.max_instance_types or len(problem.catalog)))
+    # max_instance_types <= 0: no truncation, a NodeClaim may list the whole catalog
+    m = problem.max_instance_types if problem.max_instance_types > 0 else len(problem.catalog)
+    ob = model.OutputBuffers(problem.pods.n, cap_nc, cap_nc * max(1, m))
     h = C.c_void_p()
     st = L.orc_solve_opts(C.byref(cv.view), C.byref(iv.view), C.byref(opts), C.byref(ob.view), C.byref(h))
     if st != 0:

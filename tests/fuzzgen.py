@@ -17,14 +17,21 @@ AWS = "karpenter.k8s.aws/"
 ZONES = ["test-zone-1a", "test-zone-1b", "test-zone-1c"]
 
 
-def _rand_req(rng, catalog):
+def _zone_pool(zones):
+    """The zone values a random zone requirement draws from: the catalog's zones (ZONES unless the caller names its own)
+    plus one value no catalog has; a 64-zone list leaves no room for that value in the 64-value dictionary."""
+    zs = list(ZONES if zones is None else zones)
+    return zs if len(zs) >= 64 else zs + ["us-west-2z"]
+
+
+def _rand_req(rng, catalog, zones=None):
     it = catalog[int(rng.integers(0, len(catalog)))]
     kind = int(rng.integers(0, 14))
     if kind == 0:
         return Requirement(ARCH, str(rng.choice(["In", "NotIn"])), [str(rng.choice(["amd64", "arm64"]))])
     if kind == 1:
         return Requirement(ZONE, str(rng.choice(["In", "NotIn"])),
-                           sorted(set(rng.choice(ZONES + ["us-west-2z"], size=int(rng.integers(1, 3))).tolist())))
+                           sorted(set(rng.choice(_zone_pool(zones), size=int(rng.integers(1, 3))).tolist())))
     if kind == 2:
         return Requirement(CAPACITY_TYPE, "In", [str(rng.choice(["spot", "on-demand"]))])
     if kind == 3:
@@ -54,7 +61,7 @@ def _rand_req(rng, catalog):
                        sorted(set(rng.choice(["large", "xlarge", "2xlarge", "metal", "medium"], size=2).tolist())))
 
 
-def existing_nodes(rng, catalog, n_nodes):
+def existing_nodes(rng, catalog, n_nodes, zones=None):
     """Existing (in-flight / running) nodes: labels of a catalog type (+ zone, capacity-type, a custom team label),
     available = a fraction of the type's allocatable, daemonset requests, sometimes a taint."""
     nodes = []
@@ -67,7 +74,7 @@ def existing_nodes(rng, catalog, n_nodes):
                     labels[k] = str(v[int(rng.integers(0, len(v)))])
             elif v is not None:
                 labels[k] = str(v)
-        labels[ZONE] = str(rng.choice(ZONES))
+        labels[ZONE] = str(rng.choice(ZONES if zones is None else list(zones)))
         labels[CAPACITY_TYPE] = str(rng.choice(["spot", "on-demand"]))
         if rng.random() < 0.5:
             labels["example.com/team"] = str(rng.choice(["a", "b"]))
@@ -97,14 +104,15 @@ def _existing_req(rng, n_nodes):
     return Requirement(HOSTNAME, "Exists")
 
 
-def fuzz_problem(catalog, seed, n_pods=300, n_classes=12, n_pools=3, with_min=True, with_limits=True, n_existing=0):
+def fuzz_problem(catalog, seed, n_pods=300, n_classes=12, n_pools=3, with_min=True, with_limits=True, n_existing=0,
+                 zones=None):
     rng = np.random.Generator(np.random.PCG64(seed))
     T = len(catalog)
     pools = []
     for j in range(n_pools):
         reqs = [Requirement(CAPACITY_TYPE, "In", sorted(set(rng.choice(["spot", "on-demand"], size=2).tolist())))]
         for _ in range(int(rng.integers(0, 3))):
-            reqs.append(_rand_req(rng, catalog))
+            reqs.append(_rand_req(rng, catalog, zones))
         if with_min and rng.random() < 0.3:
             reqs.append(Requirement(AWS + "instance-family", "Exists", [], int(rng.integers(2, 6))))
         labels = {"example.com/team": "a"} if rng.random() < 0.4 else {}
@@ -125,7 +133,7 @@ def fuzz_problem(catalog, seed, n_pods=300, n_classes=12, n_pools=3, with_min=Tr
                               instance_types=rows))
     classes, creqs = [], []
     for c in range(n_classes):
-        reqs = [_rand_req(rng, catalog) for _ in range(int(rng.integers(0, 3)))]
+        reqs = [_rand_req(rng, catalog, zones) for _ in range(int(rng.integers(0, 3)))]
         if n_existing and rng.random() < 0.4:
             reqs.append(_existing_req(rng, n_existing))
         tols = [Toleration("example.com/gpu", "Exists", "", "NoSchedule")] if rng.random() < 0.3 else []
@@ -145,7 +153,7 @@ def fuzz_problem(catalog, seed, n_pods=300, n_classes=12, n_pools=3, with_min=Tr
     pods = _pods_from_milli(specs)
     if rng.random() < 0.5:  # equal creation times: UID order decides ties
         pods.creation_ns[:] = pods.creation_ns[0]
-    existing = existing_nodes(rng, catalog, n_existing) if n_existing else []
+    existing = existing_nodes(rng, catalog, n_existing, zones) if n_existing else []
     return Problem(catalog, pools, classes, pods, existing)
 
 
@@ -192,9 +200,9 @@ def add_topology(rng, prob, p_term=0.6, namespaces=("default", "team-b")):
     return prob
 
 
-def fuzz_topology_problem(catalog, seed, n_pods=200, n_classes=10):
+def fuzz_topology_problem(catalog, seed, n_pods=200, n_classes=10, zones=None):
     """fuzz_problem (requirements, taints, pools, limits, minValues) plus topology terms on its classes."""
-    prob = fuzz_problem(catalog, seed, n_pods=n_pods, n_classes=n_classes)
+    prob = fuzz_problem(catalog, seed, n_pods=n_pods, n_classes=n_classes, zones=zones)
     return add_topology(np.random.Generator(np.random.PCG64(seed + 99)), prob)
 
 
@@ -253,12 +261,13 @@ def add_mutators(rng, cp, gpu_catalog=None):
 
 
 def fuzz_consolidation(catalog, seed, n_nodes=40, n_pods=200, n_candidates=None, with_min=False, pending_frac=0.15,
-                       all_spot=False, n_pools=3):
+                       all_spot=False, n_pools=3, zones=None):
     """A consolidation pass over random state: fuzz_problem's classes / pools / existing nodes, NewScheduler node order
     (initialized first, then name), candidates with their bound pods, pending pods, candidate prices around their
     offering price (so REPLACE, price-filtered NONE and DELETE all occur)."""
     from kpsim import abi, synth
-    prob = fuzz_problem(catalog, seed, n_pods=n_pods, n_classes=12, with_min=with_min, n_existing=n_nodes, n_pools=n_pools)
+    prob = fuzz_problem(catalog, seed, n_pods=n_pods, n_classes=12, with_min=with_min, n_existing=n_nodes, n_pools=n_pools,
+                        zones=zones)
     rng = np.random.Generator(np.random.PCG64(seed + 7))
     E = len(prob.existing)
     init = (rng.random(E) < 0.9).astype(np.uint8)
@@ -289,22 +298,24 @@ def fuzz_consolidation(catalog, seed, n_nodes=40, n_pods=200, n_candidates=None,
     return model.ConsolidationProblem(prob, cands, np.nonzero(owner < 0)[0].astype(np.int32), init)
 
 
-def fuzz_topology_existing_problem(catalog, seed, n_pods=200, n_classes=10, n_existing=24, n_bound=40):
+def fuzz_topology_existing_problem(catalog, seed, n_pods=200, n_classes=10, n_existing=24, n_bound=40, zones=None):
     """fuzz_topology_problem over a cluster: existing nodes (labels with zone / capacity-type / team, partial
     headroom, taints) and pods of the classes already bound to them, whose topology terms count (countDomains) and
     whose required anti-affinity blocks their nodes' domains (updateInverseAffinities)."""
-    prob = fuzz_problem(catalog, seed, n_pods=n_pods, n_classes=n_classes, n_existing=n_existing)
+    prob = fuzz_problem(catalog, seed, n_pods=n_pods, n_classes=n_classes, n_existing=n_existing, zones=zones)
     rng = np.random.Generator(np.random.PCG64(seed + 7))
     prob = add_topology(rng, prob)
     prob.bound = [(int(rng.integers(0, n_existing)), int(rng.integers(0, n_classes))) for _ in range(n_bound)]
     return prob
 
 
-def fuzz_topology_consolidation(catalog, seed, n_nodes=30, n_pods=160, n_bound=40, all_spot=False, host_affinity=False):
+def fuzz_topology_consolidation(catalog, seed, n_nodes=30, n_pods=160, n_bound=40, all_spot=False, host_affinity=False,
+                                zones=None, n_candidates=None, pending_frac=0.15):
     """fuzz_consolidation over pods with topology terms (add_topology: zonal / hostname / capacity-type spread,
     anti-affinity, zonal affinity; hostname pod affinity turned into anti-affinity unless host_affinity) plus
     non-reschedulable pods bound to random nodes (cluster.bound)."""
-    cp = fuzz_consolidation(catalog, seed, n_nodes=n_nodes, n_pods=n_pods, all_spot=all_spot)
+    cp = fuzz_consolidation(catalog, seed, n_nodes=n_nodes, n_pods=n_pods, all_spot=all_spot, zones=zones,
+                            n_candidates=n_candidates, pending_frac=pending_frac)
     rng = np.random.Generator(np.random.PCG64(seed + 123))
     prob = add_topology(rng, cp.cluster, p_term=0.4)
     for pc in prob.classes:

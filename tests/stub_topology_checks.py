@@ -75,6 +75,31 @@ def main():
     prob2.nodepools[0].requirements = list(prob2.nodepools[0].requirements) + [
         model.Requirement(model.RESERVATION_ID, "Exists", [], 2)]
     run("resv_id_min_values", lambda: solve_prep(prob2))
+    # the 64-bit word edges (tests/edge_cases.py): 64 (zone, capacity-type) slots and 64 zone values are accepted, one
+    # more of either is refused; consolidation takes max_instance_types 1..64
+    import edge_cases as EC
+    fx = catalog.load_fixtures()
+    both = ("on-demand", "spot")
+    for nz, cts in ((32, both), (33, both), (64, both[:1]), (65, both[:1])):
+        zc = EC.zoned_catalog(fx, nz, cts, 40, seed=nz)
+        run("zones_%dx%d" % (nz, len(cts)), lambda: solve_prep(EC.kat_spread(zc)))
+    for nz in (64, 63):
+        prob, _ = EC.kat_every_zone(EC.zoned_catalog(fx, nz, both[:1], 40, seed=nz))
+        prob.classes[0].requirements = prob.classes[0].requirements + [
+            model.Requirement(model.ZONE, "NotIn", [EC.FOREIGN_ZONE])]
+        run("zones_%dx1_foreign" % nz, lambda: solve_prep(prob))
+    for m in (0, 1, 64, 65):
+        cp = fuzzgen.fuzz_consolidation(EC.sample(golden, 160, 9500), 9500, n_nodes=20, n_pods=80)
+        cp.cluster.max_instance_types = m
+        run("cons_max_types_%d" % m, lambda: cons_prep(cp))
+    for m in (1, 5, 64):  # NodePools with minValues 2..5: a list of m types must be able to hold them
+        cp = fuzzgen.fuzz_consolidation(EC.sample(golden, 160, 9502), 9502, n_nodes=20, n_pods=80, with_min=True)
+        assert max(r.min_values or 0 for np_ in cp.cluster.nodepools for r in np_.requirements) in (2, 3, 4, 5)
+        cp.cluster.max_instance_types = m
+        run("cons_min_values_max_types_%d" % m, lambda: cons_prep(cp))
+    cp.cluster.max_instance_types = 1
+    cp.cluster.min_values_policy = abi.KP_MIN_VALUES_BEST_EFFORT
+    run("cons_min_values_best_effort_1", lambda: cons_prep(cp))
     ctx.close()
     print(json.dumps(out))
 

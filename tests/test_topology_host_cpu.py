@@ -62,3 +62,33 @@ def test_reservation_id_selection_beyond_64(checks):
     through ResvTab rows); minValues on that key is refused (distinct counts use 64-bit masks)"""
     assert checks["resv_id_selection"] == "ok"
     assert checks["resv_id_min_values"].startswith("KP_E_UNSUPPORTED") and "minValues" in checks["resv_id_min_values"]
+
+
+def test_slot_and_zone_value_limits(checks):
+    """64 (zone, capacity-type) offering slots and 64 values of the zone label are accepted; 33 zones x 2, 65 zones x 1
+    and 64 catalog zones plus a pod value are refused, each with its own reason (tests/test_gpu_word_edges.py runs the
+    accepted shapes on the device)"""
+    for k in ("zones_32x2", "zones_64x1", "zones_63x1_foreign"):
+        assert checks[k] == "ok", (k, checks[k])
+    for k in ("zones_33x2", "zones_65x1"):
+        assert checks[k].startswith("KP_E_UNSUPPORTED") and "64 zone x capacity-type" in checks[k], (k, checks[k])
+    v = checks["zones_64x1_foreign"]
+    assert v.startswith("KP_E_UNSUPPORTED") and "> 64 values" in v, v
+
+
+def test_consolidation_max_instance_types_limits(checks):
+    """consolidate-prepare takes max_instance_types 1..64; 65, and 0 (= the whole 160-type catalog), are refused"""
+    for m in (1, 64):
+        assert checks["cons_max_types_%d" % m] == "ok", checks["cons_max_types_%d" % m]
+    for m in (0, 65):
+        v = checks["cons_max_types_%d" % m]
+        assert v.startswith("KP_E_UNSUPPORTED") and "1..64" in v, (m, v)
+
+
+def test_consolidation_max_instance_types_below_min_values(checks):
+    """Strict minValues above max_instance_types: every NodeClaim of that NodePool would fail TruncateInstanceTypes, which
+    the probes do not model: refused.  At or above the largest minValues, and under BestEffort, the pass is accepted."""
+    v = checks["cons_min_values_max_types_1"]
+    assert v.startswith("KP_E_UNSUPPORTED") and "below a NodePool's minValues" in v, v
+    for k in ("cons_min_values_max_types_5", "cons_min_values_max_types_64", "cons_min_values_best_effort_1"):
+        assert checks[k] == "ok", (k, checks[k])
