@@ -325,13 +325,19 @@ kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out);
 
 /* Device time (ms, HIP events on the ctx stream) of the last kp_solve_execute, per phase:
  * [0] queue sort, [1] class masks, [2] template filter, [3] FFD solve kernel, [4] finalize/Truncate;
- * then (after kp_solve_fetch, KPSIM_PROFILE=1 in the environment at prepare) FFD-kernel shader-clock counters
- * [5..10]: wave-0 fast loop, its sort.Slice share, slow-path NodeClaim.Add rounds, new-NodeClaim templates, -,
- * full-pdqsort share; [11..16] per-stage evaluation cycles; then event counts [17] quick accepts, [18] slow-path
- * pods, [19] witness misses (slow-path evaluations of a NodeClaim whose class repeats), [20..23] fast-loop
- * cycles: pop, scan, quick check, quick commit; [24..34] fast-loop event counts; [35] topology quick accepts, [36..37]
- * topology prefilter setup / scan cycles; [38..41] failed NodeClaim.Add evaluations by stage: requirement merge,
- * topology narrowing, no instance type left, minValues (n up to 42). */
+ * then (after kp_solve_fetch) the FFD kernel's counters.
+ * Always exact: [16] NodeClaim.Add evaluations of in-flight NodeClaims, [17] quick accepts, [18] slow-path pods,
+ * [19] witness misses (slow-path evaluations of a NodeClaim whose class repeats), [35] topology quick accepts,
+ * [38..41] failed NodeClaim.Add evaluations by stage: requirement merge, topology narrowing, no instance type left,
+ * minValues.
+ * Profiling only — written by the diagnostic build of the solve kernel, which runs when KPSIM_PROFILE=1 is in the
+ * environment at prepare, and 0 otherwise (the production kernel carries no clock reads or diagnostic counters):
+ * shader-clock cycles [5..10]: wave-0 fast loop, its sort.Slice share, slow-path NodeClaim.Add rounds, new-NodeClaim
+ * templates, -, full-pdqsort share; [11..15] per-stage evaluation cycles; [20..23] fast-loop cycles: pop, scan, quick
+ * check, quick commit; [24..34] fast-loop event counts (n_*); [36..37] topology prefilter setup / scan cycles;
+ * [42..45] cycles of wave 0's hand-off of a pod to the block: fast-loop entry up to the first pop, the quick check
+ * that failed, window flush + candidate collection, statistics write-back + the wait for the flushed totals
+ * (n up to 46). */
 kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n);
 
 /*

@@ -410,7 +410,8 @@ struct EvalIn {
     int tmpl;                 // template of the NodeClaim (taints bit, minValues keys)
     bool compat;              // taints + Requirements.Compatible
     bool force_off;           // always apply the offering test (template filter)
-    long long* prof;          // LDS stage-cycle counters (diagnostics) or null
+    long long* prof;          // LDS counters from ST_EV_REQ on or null: evaluations and rejections by reason (always),
+                              // stage cycles (eval_wave PROF under KPSIM_PROFILE)
     int host;                 // topology hostname domain of the candidate (E + NodeClaim id)
     uint64_t held;            // lane r < ResvTab::ridw: word r of the reservations the candidate holds (0: new NodeClaim)
 };
@@ -792,7 +793,7 @@ __device__ inline void existing_topo_commit(const KpDev& d, const ClassCache& CC
 
 #define EV_STAMP(slot)                                                           \
     do {                                                                         \
-        if (a.prof) {                                                            \
+        if (PROF && d.profile && a.prof) {                                       \
             const long long _t = __builtin_amdgcn_s_memtime();                   \
             if (lane == 0) atomicAdd((unsigned long long*)&a.prof[slot], (unsigned long long)(_t - _t0)); \
             _t0 = _t;                                                            \
@@ -809,12 +810,14 @@ __device__ inline void existing_topo_commit(const KpDev& d, const ClassCache& CC
 // TEAM: every wave of the block evaluates the same candidate (tb: this evaluation's TeamBuf, rank = wave, n waves):
 // the requirement, topology and offering steps run in each wave alike, the type sweep is split over the waves by word,
 // and one block barrier joins the partial sweeps; every wave ends with the same result in its ws.
-template <bool TOPO, bool RESV = false, bool STRICT = true, bool BE = true, bool CT = false, bool TEAM = false>
+// PROF: the diagnostic twins of the Solve kernels (ffd_solve PROF): stage stamps into a.prof under KPSIM_PROFILE.
+template <bool TOPO, bool RESV = false, bool STRICT = true, bool BE = true, bool CT = false, bool TEAM = false,
+          bool PROF = false>
 __device__ __forceinline__ bool eval_wave(const KpDev& d, const EvalEnv& E, const ClassCache& CC, const EvalIn& a,
                                           WaveScratch& ws, int lane, TeamBuf* tb = nullptr, int trank = 0, int tn = 1,
                                           int* joins = nullptr) {
     const int TW = d.TW, T = d.T;
-    long long _t0 = a.prof ? __builtin_amdgcn_s_memtime() : 0;
+    long long _t0 = (PROF && d.profile && a.prof) ? __builtin_amdgcn_s_memtime() : 0;
     if (a.prof && lane == 0) atomicAdd((unsigned long long*)&a.prof[ST_EV_CALLS - ST_EV_REQ], 1ull);
     if (a.compat && !((CC.tol >> a.tmpl) & 1ull)) return false;
     const int nck = CC.nck;

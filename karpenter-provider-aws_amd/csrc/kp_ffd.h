@@ -360,19 +360,22 @@ __device__ inline void topo_record_quick(const KpDev& d, FfdShared& S, int c, in
 // wave 0: collect up to KP_NWAVES slice positions >= start whose NodeClaim has not rejected the current shape, whose
 // template's taints the pod's class tolerates (NodeClaim.Add's first test; tol bit j = template j) and that passes the
 // topology prefilter of the current pod
+// TOPO: the solve has topology groups (otherwise no pod carries a prefilter and its tests compile out)
+template <bool TOPO>
 __device__ inline void collect_candidates(const KpDev& d, FfdShared& S, const uint32_t* key, const uint16_t* ord,
                                           const uint8_t* stmpl, uint64_t tol, int N, int start, int buf, int lane) {
     int cnt = 0, pos = start, next = N;
+    const int tp_n = TOPO ? S.tp_n : 0;  // read once: the stores to cand_pos below would make every use a new LDS read
     // topology pods: at most d.topo_cands candidates per round (the first prefilter survivor usually accepts; fewer waves
     // evaluating leaves each its own SIMD)
-    const int L = S.tp_n ? d.topo_cands : KP_NWAVES;
+    const int L = tp_n ? d.topo_cands : KP_NWAVES;
     while (pos < N) {
         const int p = pos + lane;
         bool c = p < N && !(key[p] >> 31);
         if (c) c = (tol >> stmpl[ord[p]]) & 1ull;
-        if (S.tp_n && c) c = topo_prefilter_pass(d, S, ord[p]);
+        if (tp_n && c) c = topo_prefilter_pass(d, S, ord[p]);
         const uint64_t m0 = __ballot(c);
-        if (S.tp_n && m0 && cnt + __popcll(m0) < L) {
+        if (tp_n && m0 && cnt + __popcll(m0) < L) {
             // topology pods: the first prefilter survivor usually accepts; end the round with this window rather than
             // paying the prefilter's loads for up to 8 candidates (the next round continues after it)
             const int rank = cnt + __popcll(m0 & ((1ull << lane) - 1ull));
@@ -433,7 +436,8 @@ __device__ inline void limit_mask_update(const KpDev& d, int j, int lane) {
     if (lane < d.TW) d.tmpl_lmask[(size_t)j * d.TW + lane] = mine;
 }
 
-__device__ __forceinline__ long long prof_clock(const KpDev& d) { return d.profile ? __builtin_amdgcn_s_memtime() : 0; }
+// the shader clock in a profiling run (ffd_solve's prof: a compile-time false in the production instantiations)
+__device__ __forceinline__ long long prof_clock(bool prof) { return prof ? __builtin_amdgcn_s_memtime() : 0; }
 
 
 // The winner's reservations (one wave; lane r: word r of the held set): ReservationManager.Reserve for the
@@ -587,9 +591,14 @@ __device__ inline void block_sort_move(FfdShared& S, SortSlice sl, int tid, int 
 #ifndef KP_NOOP_RESV
 #define KP_NOOP_RESV 1        // A/B builds: 0 compiles the no-op merge quick accept out of the RESV instantiations
 #endif
-template <bool RESV, bool TOPO, bool PREF, bool HBM = false>
+// PROF: the diagnostic twin of an entry point (kp_ffd_prof_*.hip; launched when KPSIM_PROFILE or KPSIM_TRACE_POD is
+// set): stage stamps (s_memtime), the cyc_* / n_* / why counters and the trace records.  The production instantiations
+// compile all of it out: those statistics read 0 there, every other one is exact in both.
+template <bool RESV, bool TOPO, bool PREF, bool HBM = false, bool PROF = false>
 __device__ __forceinline__ void ffd_solve(KpDev d) {
     constexpr bool TOPO_ON = KP_TOPO_ON && TOPO;  // the solve has topology groups
+    const bool prof = PROF && d.profile;
+    int* const trace = PROF ? d.trace : nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     FfdShared& S = *reinterpret_cast<FfdShared*>(smem);
     uint32_t* const skey = HBM ? d.g_key : reinterpret_cast<uint32_t*>(smem + d.off_key);    // len(Pods) by slice position
@@ -755,10 +764,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
     for (int ai = 0; ai < KP_LDS_AXES; ai++) vq[ai] = 0;
 
     for (;;) {
-        const long long c_top = (d.profile && tid == 0) ? __builtin_amdgcn_s_memtime() : 0;
+        const long long c_top = (prof && tid == 0) ? __builtin_amdgcn_s_memtime() : 0;
         // ================= wave 0: the fast loop =================
         if (wave == 0) {
-            const long long c_in = prof_clock(d);
+            const long long c_in = prof_clock(prof);
             const int N = S.N;
             int qhead = S.qhead, qcount = S.qcount;
             int seq = S.seq, prev_shape = S.prev_shape, dkind = S.dirty_kind, dpos = S.dirty_pos;
@@ -809,6 +818,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             long long cqpop = 0, cqscan = 0, cqcheck = 0, cqcommit = 0;
             long long n_noinv = 0, n_winmove = 0, n_ldssort = 0, n_pivot = 0, n_winload = 0, n_flush = 0, n_shape = 0;
             long long n_r2 = 0, n_rwb = 0, n_rout = 0, n_batch = 0;
+            long long ho_entry = -1, ho_fail = 0, t_f = 0;  // PROF: the hand-off's parts (ST_HANDOFF)
 
             // ---- slice window: lane i mirrors slice position wb + i and its NodeClaim (authoritative while valid) ----
             int wb = -1;
@@ -818,6 +828,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             int wcnt = 0;                                       // current-shape pods placed since the last flush
 #pragma unroll
             for (int ai = 0; ai < KP_LDS_AXES; ai++) wh[ai] = -1;
+            // resources the current shape requests (bit r: shape_req[r] != 0): the pending-total flush visits these alone
+            // (lane r holds shape_req[r]: the flush reads it from the register, not from LDS)
+            int64_t sreq = lane < R ? S.shape_req[lane] : 0;
+            uint32_t rmask = (uint32_t)ballot(sreq != 0);
             auto absorbed = [&](uint32_t m) -> bool {
                 return (int)(m & 0xFFFFu) == c || ((tl >> 63) && ((tl >> (m >> 16)) & 1ull));
             };
@@ -832,9 +846,9 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     if ((int)wo < NQ)
                         for (int ai = 0; ai < A; ai++) shr[ai * NQ + wo] = wh[ai];
                     if (wcnt)
-                        for (int r = 0; r < R; r++) {
-                            const int64_t x = S.shape_req[r];
-                            if (x) atomicAdd((unsigned long long*)&d.nc_req[(size_t)wo * R + r], (unsigned long long)(x * wcnt));
+                        for (uint32_t m = rmask; m; m &= m - 1) {  // the shape's non-zero requests, in resource order
+                            const int r = __ffs(m) - 1;
+                            atomicAdd((unsigned long long*)&d.nc_req[(size_t)wo * R + r], (unsigned long long)(rl64(sreq, r) * wcnt));
                         }
                 }
                 wcnt = 0;
@@ -869,7 +883,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 p = S.cur_pod;
                 off = -1;
                 shape = prev_shape;
-                t_a = prof_clock(d);
+                t_a = prof_clock(prof);
               } else {
                 if (qcount == 0 || err) {
                     done = 1;
@@ -903,7 +917,8 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     qw_used = 0;
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 }
-                t_a = prof_clock(d);
+                t_a = prof_clock(prof);
+                if (PROF && ho_entry < 0) ho_entry = t_a - c_in;
                 off = qw_used;
                 if (rl32(vlast, off) == qcount) {
                     done = 1;
@@ -931,7 +946,11 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     tl = rl64(vtol, off);
 #pragma unroll
                     for (int ai = 0; ai < KP_LDS_AXES; ai++) pq[ai] = rl32(vq[ai], off);
-                    if (lane < R) S.shape_req[lane] = qw_req[off * R + lane];
+                    {
+                        sreq = lane < R ? qw_req[off * R + lane] : 0;
+                        if (lane < R) S.shape_req[lane] = sreq;
+                        rmask = (uint32_t)ballot(sreq != 0);
+                    }
                     wa = wb >= 0 && wb + lane < N && absorbed(wm);
                     sstart = 0;
                     prev_shape = shape;
@@ -1000,7 +1019,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 }
               }
                 scanned += N;
-                const long long t_b = prof_clock(d);
+                const long long t_b = prof_clock(prof);
                 cqpop += t_b - t_a;
                 // sort.Slice(s.newNodeClaims, by len(Pods)) at the start of add(): at most one element changed since
                 // the last sort (dkind 1: position dpos gained a pod; dkind 2: a NodeClaim was appended)
@@ -1074,7 +1093,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                     sfast += how == 1;
                     sfull += how == 2;
-                    const long long c1 = prof_clock(d);
+                    const long long c1 = prof_clock(prof);
                     csort += c1 - t_b;
                     if (how == 2) csfull += c1 - t_b;
                     // positions < dpos are untouched by a stable move of dpos and rejected this shape (when the
@@ -1097,7 +1116,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     break;
                 }
                 // first NodeClaim in slice order (from sstart) that has not rejected this shape
-                const long long t_c = prof_clock(d);
+                const long long t_c = prof_clock(prof);
                 int f = N;
                 for (int pos = sstart; pos < N;) {
                     if (wb < 0 || pos < wb || pos >= wb + 64) {
@@ -1112,7 +1131,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     }
                     pos = wb + 64;
                 }
-                const long long t_d = prof_clock(d);
+                const long long t_d = prof_clock(prof);
                 cqscan += t_d - t_c;
                 if (f < N) {
                     const int fl = f - wb;
@@ -1132,7 +1151,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                             }
                             if (lane == 0) {
                                 slast[nc] = (uint16_t)c;  // its requirements are a subset of the class's
-                                if (d.profile) S.st[ST_SLOW_WHY + 4]++;
+                                if (prof) S.st[ST_SLOW_WHY + 4]++;
                             }
                             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                             okm |= 1ull << fl;
@@ -1268,13 +1287,15 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         sstart = f;
                         nquick += m;
                         n_batch++;
-                        const long long t_e = prof_clock(d);
+                        const long long t_e = prof_clock(prof);
                         cqcheck += t_e - t_d;
                         continue;
                     }
                 }
                 // slow path: the whole block evaluates this pod
-                if (d.profile) {  // KPSIM_PROFILE: why the quick accept does not apply
+                t_f = prof_clock(prof);
+                ho_fail = t_f - t_d;
+                if (prof) {  // KPSIM_PROFILE: why the quick accept does not apply
                     const bool fa = f < N && rl32(wa ? 1 : 0, (f - wb) & 63) != 0;
                     if (lane == 0) S.st[ST_SLOW_WHY + (f >= N ? 0 : A == 0 ? 3 : !fa ? 1 : 2)]++;
                 }
@@ -1286,11 +1307,12 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     S.cls_fill = S.CC.cls != c;  // decided before the barrier: fill_class_cache rewrites CC.cls
                     S.topo_pod = 0;
                 }
-                collect_candidates(d, S, skey, sord, stmpl, ~0ull, N, f, 0, lane);
+                collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, ~0ull, N, f, 0, lane);
                 break;
             }
             win_flush();
             ex_flush();
+            const long long t_w = prof_clock(prof);
             if (lane == 0) {
                 S.xstart = xstart;
                 S.st[ST_EXIST_PLACED] += nexist;
@@ -1317,25 +1339,31 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 S.st[ST_SLOW] += done ? 0 : 1;
                 S.st[ST_SORT_FAST] += sfast;
                 S.st[ST_SORT_FULL] += sfull;
-                S.st[ST_CYC_SORT] += csort;
-                S.st[ST_CYC_SORT_FULL] += csfull;
-                S.st[ST_CYC_QPOP] += cqpop;
-                S.st[ST_CYC_QSCAN] += cqscan;
-                S.st[ST_CYC_QCHECK] += cqcheck;
-                S.st[ST_CYC_QCOMMIT] += cqcommit;
-                S.st[ST_N_NOINV] += n_noinv;
-                S.st[ST_N_WINMOVE] += n_winmove;
-                S.st[ST_N_LDSSORT] += n_ldssort;
-                S.st[ST_N_PIVOT] += n_pivot;
-                S.st[ST_N_WINLOAD] += n_winload;
-                S.st[ST_N_FLUSH] += n_flush;
-                S.st[ST_N_SHAPE] += n_shape;
-                S.st[ST_N_SHAPE + 1] += n_r2;
-                S.st[ST_N_SHAPE + 2] += n_rwb;
-                S.st[ST_N_SHAPE + 3] += n_rout;
-                S.st[ST_N_SHAPE + 4] += n_batch;
-
-                S.st[ST_CYC_POP] += prof_clock(d) - c_in;
+                if (PROF) {  // the diagnostic twin alone carries the stage cycles and the n_* counters
+                    S.st[ST_CYC_SORT] += csort;
+                    S.st[ST_CYC_SORT_FULL] += csfull;
+                    S.st[ST_CYC_QPOP] += cqpop;
+                    S.st[ST_CYC_QSCAN] += cqscan;
+                    S.st[ST_CYC_QCHECK] += cqcheck;
+                    S.st[ST_CYC_QCOMMIT] += cqcommit;
+                    S.st[ST_N_NOINV] += n_noinv;
+                    S.st[ST_N_WINMOVE] += n_winmove;
+                    S.st[ST_N_LDSSORT] += n_ldssort;
+                    S.st[ST_N_PIVOT] += n_pivot;
+                    S.st[ST_N_WINLOAD] += n_winload;
+                    S.st[ST_N_FLUSH] += n_flush;
+                    S.st[ST_N_SHAPE] += n_shape;
+                    S.st[ST_N_SHAPE + 1] += n_r2;
+                    S.st[ST_N_SHAPE + 2] += n_rwb;
+                    S.st[ST_N_SHAPE + 3] += n_rout;
+                    S.st[ST_N_SHAPE + 4] += n_batch;
+                    // the hand-off to the block, by part: entry up to the first pop; the quick check that failed; the
+                    // window flush and the candidate collection (the write-back and its wait are stamped below)
+                    S.st[ST_HANDOFF] += ho_entry < 0 ? 0 : ho_entry;
+                    S.st[ST_HANDOFF + 1] += ho_fail;
+                    S.st[ST_HANDOFF + 2] += t_f ? t_w - t_f : 0;
+                    S.st[ST_CYC_POP] += prof_clock(prof) - c_in;
+                }
             }
             if (lane < KP_LDS_AXES) {
 #pragma unroll
@@ -1343,11 +1371,12 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     if (lane == ai) S.cur_pq[ai] = pq[ai];
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // flushed request totals have reached L2
+            if (prof && lane == 0) S.st[ST_HANDOFF_WB] += __builtin_amdgcn_s_memtime() - t_w;
         }
         __syncthreads();
         if (S.done) break;
-        const long long c_slow = prof_clock(d);
-        if (d.profile && tid == 0) S.st[ST_SEG + 0] += c_slow - c_top;
+        const long long c_slow = prof_clock(prof);
+        if (prof && tid == 0) S.st[ST_SEG + 0] += c_slow - c_top;
         const int pod = S.cur_pod;
         if (TOPO_ON && S.topo_pod && d.E > 0 && !S.topo_exdone) {
             // ================= a pod with topology terms: existing nodes first (wave 0) =================
@@ -1380,7 +1409,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             // prefilter of this pod's groups, first surviving NodeClaim in slice order; quick accept when it has
             // absorbed the class, every narrowed key is a single admitted domain and the witness fits; otherwise
             // the block evaluates candidates from there
-            const long long t0 = prof_clock(d);
+            const long long t0 = prof_clock(prof);
             const int c = S.cur_cls, N = S.N;
             const uint32_t cfl = d.cls_flags[c];
             const int scan_from = S.scan_start;
@@ -1393,7 +1422,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             if (cfl & CF_TOPO_CONS) topo_prefilter_setup(d, S, c, wave, lane);
             __syncthreads();  // every group's entry and TopoSnap row
             if (tid == 0 && (cfl & CF_TOPO_CONS)) S.tp_cls = c;  // read by the next setup, behind the next slow-path barrier
-            const long long t1 = prof_clock(d);
+            const long long t1 = prof_clock(prof);
             const int f = topo_scan_block(d, S, skey, sord, stmpl, ctol, N, scan_from, S.bred, wave, lane);
 #else
             int f = N;
@@ -1406,14 +1435,14 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 if (cfl & CF_TOPO_CONS)
                     for (int w = 0; w < KP_NWAVES; w++) topo_prefilter_setup(d, S, c, w, lane);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                t1 = prof_clock(d);
+                t1 = prof_clock(prof);
                 f = topo_scan(d, S, skey, sord, stmpl, ctol, N, scan_from, lane);
             }
 #endif
-            const long long t2 = prof_clock(d);
+            const long long t2 = prof_clock(prof);
             if (wave == 0) {
                 bool quick = false;
-                if (d.profile && lane == 0) {  // KPSIM_PROFILE: why the topology quick accept does not apply
+                if (prof && lane == 0) {  // KPSIM_PROFILE: why the topology quick accept does not apply
                     const int nc = f < N ? sord[f] : 0;
                     const int why = f >= N ? 0 : !(cfl & CF_TOPO_QREC) ? 1 : nc >= NQ ? 2
                                   : !(slast[nc] == (uint16_t)c || ((cfl & CF_NOKEYS) && ((d.tol[c] >> stmpl[nc]) & 1ull))) ? 3 : 4;
@@ -1424,11 +1453,11 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     const bool absd = slast[nc] == (uint16_t)c || ((cfl & CF_NOKEYS) && ((d.tol[c] >> tm) & 1ull));
                     bool ok = nc < NQ;
                     for (int ai = 0; ai < A && ok; ai++) ok = S.cur_pq[ai] <= shr[ai * NQ + nc];
-                    if (d.profile && lane == 0 && nc < NQ && ok) S.st[ST_TQ_WHY + 5]++;  // witness fits
+                    if (prof && lane == 0 && nc < NQ && ok) S.st[ST_TQ_WHY + 5]++;  // witness fits
                     ok = ok && topo_pinned(d, S, nc, lane);
                     // a NodeClaim that has not absorbed the class: quick when the Add's merge changes nothing
                     const bool noop = ok && !absd && merge_noop(d, S, nc, c, lane);
-                    if (d.profile && lane == 0 && noop) S.st[ST_TQ_WHY + 6]++;
+                    if (prof && lane == 0 && noop) S.st[ST_TQ_WHY + 6]++;
                     quick = ok && (absd || noop);
                     if (noop && lane == 0) slast[nc] = (uint16_t)c;  // its requirements are a subset of the class's
                     if (quick) {
@@ -1449,14 +1478,14 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     }
                 }
-                if (!quick) collect_candidates(d, S, skey, sord, stmpl, ctol, N, f, 0, lane);
+                if (!quick) collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, ctol, N, f, 0, lane);
                 if (lane == 0) {
                     S.topo_quick = quick;
                     if (quick) {  // nothing reads these before the next slow-path entry (behind wave 0's fast loop)
                         S.tp_n = 0;
                         S.topo_pod = 0;
                     }
-                    if (d.profile) {
+                    if (prof) {
                         S.st[ST_CYC_TSETUP] += t1 - t0;
                         S.st[ST_CYC_TSCAN] += t2 - t1;
                     }
@@ -1464,7 +1493,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             }
             __syncthreads();
             if (S.topo_quick) {
-                if (d.profile && tid == 0) {
+                if (prof && tid == 0) {
                     S.st[ST_TQ_ITERS]++;
                     S.st[ST_TQ_CYC] += __builtin_amdgcn_s_memtime() - c_slow;
                 }
@@ -1473,9 +1502,9 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
         }
         long long c_ev0 = 0;
         {
-            const long long cf0 = (d.profile && tid == 0) ? __builtin_amdgcn_s_memtime() : 0;
+            const long long cf0 = (prof && tid == 0) ? __builtin_amdgcn_s_memtime() : 0;
             if (S.cls_fill) fill_class_cache<TOPO>(d, S.cur_cls, S.CC, tid, nthr, TOPO ? S.born : 0ull);
-            if (d.profile && tid == 0) {
+            if (prof && tid == 0) {
                 c_ev0 = __builtin_amdgcn_s_memtime();
                 S.st[ST_SLOW_WHY + 10] += c_ev0 - cf0;
                 S.st[ST_SEG + 1] += cf0 - c_slow;
@@ -1488,8 +1517,8 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
         // a pod with topology terms: its candidates one at a time, each evaluated by the whole block (the type sweep
         // split over the waves; the first candidate that passes the prefilter usually accepts), in slice order
         const bool team = TOPO_ON && S.topo_pod && d.team_eval;
-        if (d.trace && pod == d.trace_pod && wave == 0) {  // diagnostics: the slice as the slow path sees it
-            int* sl = d.trace + 1 + 6 * KP_TRACE_N;
+        if (trace && pod == d.trace_pod && wave == 0) {  // diagnostics: the slice as the slow path sees it
+            int* sl = trace + 1 + 6 * KP_TRACE_N;
             if (lane == 0) {
                 sl[0] = S.N;
                 sl[1] = S.scan_start;
@@ -1514,16 +1543,16 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 a.tmpl = d.nc_tmpl[nc];
                 a.compat = true;
                 a.force_off = false;
-                a.prof = (d.profile && wave == 0) ? &S.st[ST_EV_REQ] : nullptr;
+                a.prof = wave == 0 ? &S.st[ST_EV_REQ] : nullptr;
                 a.host = d.E + nc;
                 a.held = (RESV && d.resv_on) ? held_word(d, nc, lane) : 0ull;
                 // the buffer by the joins reached so far, not by candidate index: a candidate rejected before the join
                 // (no barrier) must not flip the parity
                 TeamBuf* const tb = &S.team[tjoins & 1];
                 const bool ok = (S.CC.flags & CF_TOPO_CONS)
-                                    ? eval_wave<true, RESV, true, PREF, false, true>(d, E, S.CC, a, S.ws[wave], lane, tb,
+                                    ? eval_wave<true, RESV, true, PREF, false, true, PROF>(d, E, S.CC, a, S.ws[wave], lane, tb,
                                                                                      wave, KP_NWAVES, &tjoins)
-                                    : eval_wave<false, RESV, true, PREF, false, true>(d, E, S.CC, a, S.ws[wave], lane,
+                                    : eval_wave<false, RESV, true, PREF, false, true, PROF>(d, E, S.CC, a, S.ws[wave], lane,
                                                                                       tb, wave, KP_NWAVES, &tjoins);
                 if (wave == 0 && lane == 0) {
                     S.fastp[b][i] = 0;
@@ -1542,7 +1571,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             }
             if (win >= 0 || S.scan_done[b]) break;
             if (wave == 0)
-                collect_candidates(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b], b ^ 1, lane);
+                collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b], b ^ 1, lane);
             __syncthreads();
             round++;
         }
@@ -1566,14 +1595,14 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 a.tmpl = tm;
                 a.compat = true;
                 a.force_off = false;
-                a.prof = (d.profile && wave == 0) ? &S.st[ST_EV_REQ] : nullptr;
+                a.prof = wave == 0 ? &S.st[ST_EV_REQ] : nullptr;
                 a.host = d.E + nc;
                 a.held = (RESV && d.resv_on) ? held_word(d, nc, lane) : 0ull;
                 TeamBuf* const tb = &S.team[tjoins & 1];
                 const bool ok = (TOPO_ON && (S.CC.flags & CF_TOPO_CONS))
-                                    ? eval_wave<true, RESV, true, PREF, false, true>(d, E, S.CC, a, S.ws[wave], lane, tb,
+                                    ? eval_wave<true, RESV, true, PREF, false, true, PROF>(d, E, S.CC, a, S.ws[wave], lane, tb,
                                                                                      wave, KP_NWAVES, &tjoins)
-                                    : eval_wave<false, RESV, true, PREF, false, true>(d, E, S.CC, a, S.ws[wave], lane,
+                                    : eval_wave<false, RESV, true, PREF, false, true, PROF>(d, E, S.CC, a, S.ws[wave], lane,
                                                                                       tb, wave, KP_NWAVES, &tjoins);
                 if (wave == 0 && lane == 0) {
                     S.fastp[0][0] = 0;
@@ -1584,7 +1613,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     }
                     if (!ok && !S.ws[0].memo_ok) S.rej_volatile = 1;
                     S.st[ST_NC_EVALS]++;
-                    if (d.profile) S.st[ST_SLOW_WHY + 8]++;
+                    if (prof) S.st[ST_SLOW_WHY + 8]++;
                 }
                 first = 1;
                 if (ok) {
@@ -1609,7 +1638,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 a.tmpl = d.nc_tmpl[nc];
                 a.compat = true;
                 a.force_off = false;
-                a.prof = d.profile ? &S.st[ST_EV_REQ] : nullptr;
+                a.prof = &S.st[ST_EV_REQ];
                 a.host = d.E + nc;
                 a.held = (RESV && d.resv_on) ? held_word(d, nc, lane) : 0ull;
                 // a NodeClaim that keeps reserved offerings re-runs the whole Add (its reservations are recomputed)
@@ -1617,12 +1646,12 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                                   (slast[nc] == (uint16_t)S.cur_cls || ((S.CC.flags & CF_NOKEYS) && ((S.CC.tol >> a.tmpl) & 1ull)));
                 if (fast && lane == 0) S.ws[wave].memo_ok = 1;
                 const bool ok = fast ? eval_fits_only<PREF>(d, E, a, S.ws[wave], lane)
-                                : (TOPO_ON && (S.CC.flags & CF_TOPO_CONS)) ? eval_wave<true, RESV, true, PREF>(d, E, S.CC, a, S.ws[wave], lane)
-                                                              : eval_wave<false, RESV, true, PREF>(d, E, S.CC, a, S.ws[wave], lane);
-                if (d.trace && (pod == d.trace_pod || (S.cur_cls == -2 - d.trace_pod && pod <= d.trace_max)) && lane == 0) {
-                    const int i = atomicAdd(&d.trace[0], 1);
+                                : (TOPO_ON && (S.CC.flags & CF_TOPO_CONS)) ? eval_wave<true, RESV, true, PREF, false, false, PROF>(d, E, S.CC, a, S.ws[wave], lane)
+                                                              : eval_wave<false, RESV, true, PREF, false, false, PROF>(d, E, S.CC, a, S.ws[wave], lane);
+                if (trace && (pod == d.trace_pod || (S.cur_cls == -2 - d.trace_pod && pod <= d.trace_max)) && lane == 0) {
+                    const int i = atomicAdd(&trace[0], 1);
                     {  // ring of the last KP_TRACE_N entries
-                        int* e = d.trace + 1 + 6 * (i % KP_TRACE_N);
+                        int* e = trace + 1 + 6 * (i % KP_TRACE_N);
                         e[0] = pod;
                         e[1] = nc;
                         e[2] = ok;
@@ -1654,18 +1683,18 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             if (tid == 0) S.st[ST_NC_EVALS] += nc_ > f0 ? nc_ - f0 : 0;
             if (win >= 0 || S.scan_done[b]) break;
             if (wave == 0)
-                collect_candidates(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b], b ^ 1, lane);
+                collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b], b ^ 1, lane);
             __syncthreads();
             round++;
         }
         long long c_ev = 0;
-        if (tid == 0 && d.profile) {
+        if (tid == 0 && prof) {
             const long long t1 = __builtin_amdgcn_s_memtime();
             S.st[ST_CYC_SCAN] += t1 - c_slow;
             S.st[ST_SEG + 3] += t1 - c_ev0;
             c_ev = t1;
         }
-        if (d.profile && tid == 0 && !S.topo_pod)  // KPSIM_PROFILE: where the slow path's pods land
+        if (prof && tid == 0 && !S.topo_pod)  // KPSIM_PROFILE: where the slow path's pods land
             S.st[ST_SLOW_WHY + (win < 0 ? 7 : (round == 0 && win == 0) ? 5 : 6)]++;
         if (win >= 0) {
             // the wave whose scratch holds the accepted Add (team: every wave's does)
@@ -1696,10 +1725,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     // every position before the winner rejected this shape for good, unless rejections depended on
                     // topology counts (not memoised; the next pod of the shape rescans them)
                     S.scan_start = ((S.CC.flags & CF_TOPO) || S.rej_volatile) ? 0 : pos;
-                    if (d.trace && S.cur_cls == -2 - d.trace_pod && pod <= d.trace_max) {
-                        const int i = atomicAdd(&d.trace[0], 1);
+                    if (trace && S.cur_cls == -2 - d.trace_pod && pod <= d.trace_max) {
+                        const int i = atomicAdd(&trace[0], 1);
                         {
-                            int* e = d.trace + 1 + 6 * (i % KP_TRACE_N);
+                            int* e = trace + 1 + 6 * (i % KP_TRACE_N);
                             e[0] = pod;
                             e[1] = -1000 - nc;
                             e[2] = S.scan_start;
@@ -1715,7 +1744,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             }
         } else {
             // ================= new NodeClaim from the templates (NodePool weight order) =================
-            const long long c_t = prof_clock(d);
+            const long long c_t = prof_clock(prof);
             // NewNodeClaim(template jj) for the pod, by wave cw (whose scratch holds the template's accepted Add)
             auto commit_tmpl = [&](int jj, int cw) {
                 const int n = S.N;
@@ -1792,11 +1821,20 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     a.held = 0;
                     TeamBuf* const tbuf = &S.team[tjoins & 1];
                     const bool ok = (TOPO_ON && (S.CC.flags & CF_TOPO_CONS))
-                                        ? eval_wave<true, RESV, true, PREF, false, true>(d, E, S.CC, a, S.ws[wave], lane, tbuf,
+                                        ? eval_wave<true, RESV, true, PREF, false, true, PROF>(d, E, S.CC, a, S.ws[wave], lane, tbuf,
                                                                                          wave, KP_NWAVES, &tjoins)
-                                        : eval_wave<false, RESV, true, PREF, false, true>(d, E, S.CC, a, S.ws[wave], lane,
+                                        : eval_wave<false, RESV, true, PREF, false, true, PROF>(d, E, S.CC, a, S.ws[wave], lane,
                                                                                           tbuf, wave, KP_NWAVES, &tjoins);
                     if (tid == 0) S.st[ST_TMPL_EVALS]++;
+                    if (trace && pod == d.trace_pod && tid == 0) {  // the entry of the per-wave template path below
+                        const int i = atomicAdd(&trace[0], 1);
+                        int* e = trace + 1 + 6 * (i % KP_TRACE_N);
+                        e[0] = -1;
+                        e[1] = -1 - j;
+                        e[2] = ok;
+                        e[3] = S.ws[0].memo_ok;
+                        e[4] = e[5] = 0;
+                    }
                     if (ok) {
                         twin = j;
                         break;
@@ -1827,13 +1865,13 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         a.prof = nullptr;
                         a.host = d.E + S.N;  // NewNodeClaim's fresh hostname (no pod counted there yet)
                         a.held = 0;
-                        ok = (TOPO_ON && (S.CC.flags & CF_TOPO_CONS)) ? eval_wave<true, RESV, true, PREF>(d, E, S.CC, a, S.ws[wave], lane)
-                                                         : eval_wave<false, RESV, true, PREF>(d, E, S.CC, a, S.ws[wave], lane);
+                        ok = (TOPO_ON && (S.CC.flags & CF_TOPO_CONS)) ? eval_wave<true, RESV, true, PREF, false, false, PROF>(d, E, S.CC, a, S.ws[wave], lane)
+                                                         : eval_wave<false, RESV, true, PREF, false, false, PROF>(d, E, S.CC, a, S.ws[wave], lane);
                     }
-                    if (d.trace && pod == d.trace_pod && lane == 0) {
-                        const int i = atomicAdd(&d.trace[0], 1);
+                    if (trace && pod == d.trace_pod && lane == 0) {
+                        const int i = atomicAdd(&trace[0], 1);
                         {
-                            int* e = d.trace + 1 + 6 * (i % KP_TRACE_N);
+                            int* e = trace + 1 + 6 * (i % KP_TRACE_N);
                             e[0] = -1;
                             e[1] = -1 - j;
                             e[2] = ok;
@@ -1914,7 +1952,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 __syncthreads();  // tacc is rewritten by the next template batch
             }
             if (tid == 0) {
-                if (d.profile) S.st[ST_CYC_TMPL] += __builtin_amdgcn_s_memtime() - c_t;
+                if (prof) S.st[ST_CYC_TMPL] += __builtin_amdgcn_s_memtime() - c_t;
                 if (twin < 0) {  // preferences.Relax, then Queue.Push(pod, relaxed)
                     const int tail = (S.qhead + S.qcount) % P;
                     d.qbuf[tail] = pod;
@@ -1944,7 +1982,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             S.topo_pod = 0;
         }
         __syncthreads();
-        if (tid == 0 && d.profile) {  // commit / templates
+        if (tid == 0 && prof) {  // commit / templates
             S.st[ST_SLOW_WHY + 9] += __builtin_amdgcn_s_memtime() - c_ev;
             S.st[ST_SEG + 4] += __builtin_amdgcn_s_memtime() - c_ev;
         }
@@ -1991,3 +2029,13 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
 
 }  // namespace KP_WNS
 using namespace KP_WNS;
+
+// A Solve kernel entry point: ffd_solve<RESV, TOPO, PREF, HBM> under its own name, so kernel traces tell the
+// instantiations apart.  A unit compiled with KP_FFD_PROF (kp_ffd_prof_*.hip) defines the diagnostic twin name_prof.
+#ifdef KP_FFD_PROF
+#define KP_FFD_ENTRY(name, ...) \
+    __global__ __launch_bounds__(KP_NWAVES * 64) void name##_prof(KpDev d) { ffd_solve<__VA_ARGS__, true>(d); }
+#else
+#define KP_FFD_ENTRY(name, ...) \
+    __global__ __launch_bounds__(KP_NWAVES * 64) void name(KpDev d) { ffd_solve<__VA_ARGS__, false>(d); }
+#endif

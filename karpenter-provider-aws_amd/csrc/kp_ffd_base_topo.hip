@@ -8,7 +8,9 @@
 #define KP_NWAVES KP_NWAVES_TOPO
 #include "kp_ffd.h"
 
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_topo_kernel(KpDev d) { ffd_solve<false, true, false>(d); }
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_topo_hbm_kernel(KpDev d) { ffd_solve<false, true, false, true>(d); }
+KP_FFD_ENTRY(ffd_topo_kernel, false, true, false, false)
+KP_FFD_ENTRY(ffd_topo_hbm_kernel, false, true, false, true)
 
+#ifndef KP_FFD_PROF  // one definition: the twin unit (kp_ffd_prof_base_topo.hip) includes this file
 size_t kp_ffd_shared_bytes_topo() { return sizeof(FfdShared); }
+#endif

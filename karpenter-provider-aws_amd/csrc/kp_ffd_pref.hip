@@ -2,5 +2,5 @@
 // with the slice arrays in LDS or HBM).  ffd_solve is in kp_ffd.h; the launcher is kp_launch_ffd (kp_kernels.hip).
 #include "kp_ffd.h"
 
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_pref_kernel(KpDev d) { ffd_solve<false, false, true>(d); }
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_pref_hbm_kernel(KpDev d) { ffd_solve<false, false, true, true>(d); }
+KP_FFD_ENTRY(ffd_pref_kernel, false, false, true, false)
+KP_FFD_ENTRY(ffd_pref_hbm_kernel, false, false, true, true)

@@ -2,5 +2,5 @@
 // with the slice arrays in LDS or HBM).  ffd_solve is in kp_ffd.h; the launcher is kp_launch_ffd (kp_kernels.hip).
 #include "kp_ffd.h"
 
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_pref_resv_kernel(KpDev d) { ffd_solve<true, false, true>(d); }
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_pref_resv_hbm_kernel(KpDev d) { ffd_solve<true, false, true, true>(d); }
+KP_FFD_ENTRY(ffd_pref_resv_kernel, true, false, true, false)
+KP_FFD_ENTRY(ffd_pref_resv_hbm_kernel, true, false, true, true)

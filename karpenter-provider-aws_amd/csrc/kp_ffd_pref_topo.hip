@@ -8,5 +8,5 @@
 #define KP_NWAVES KP_NWAVES_TOPO
 #include "kp_ffd.h"
 
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_pref_topo_kernel(KpDev d) { ffd_solve<false, true, true>(d); }
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_pref_topo_hbm_kernel(KpDev d) { ffd_solve<false, true, true, true>(d); }
+KP_FFD_ENTRY(ffd_pref_topo_kernel, false, true, true, false)
+KP_FFD_ENTRY(ffd_pref_topo_hbm_kernel, false, true, true, true)

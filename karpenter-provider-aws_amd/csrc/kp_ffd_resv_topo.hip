@@ -8,5 +8,5 @@
 #define KP_NWAVES KP_NWAVES_TOPO
 #include "kp_ffd.h"
 
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_resv_topo_kernel(KpDev d) { ffd_solve<true, true, false>(d); }
-__global__ __launch_bounds__(KP_NWAVES * 64) void ffd_resv_topo_hbm_kernel(KpDev d) { ffd_solve<true, true, false, true>(d); }
+KP_FFD_ENTRY(ffd_resv_topo_kernel, true, true, false, false)
+KP_FFD_ENTRY(ffd_resv_topo_hbm_kernel, true, true, false, true)

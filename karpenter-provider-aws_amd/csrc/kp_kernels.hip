@@ -119,24 +119,38 @@ __global__ __launch_bounds__(64) void template_init_kernel(KpDev d) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Solve: the ffd_solve instantiations (kp_ffd.h), defined in kp_ffd_{base,resv,pref,pref_resv}.hip
+// Solve: the ffd_solve instantiations (kp_ffd.h), defined in kp_ffd_{base,resv,pref,pref_resv}[_topo].hip
 // ------------------------------------------------------------------------------------------------
-__global__ void ffd_kernel(KpDev d);
-__global__ void ffd_topo_kernel(KpDev d);
-__global__ void ffd_resv_kernel(KpDev d);
-__global__ void ffd_resv_topo_kernel(KpDev d);
-__global__ void ffd_pref_kernel(KpDev d);
-__global__ void ffd_pref_topo_kernel(KpDev d);
-__global__ void ffd_pref_resv_kernel(KpDev d);
-__global__ void ffd_pref_resv_topo_kernel(KpDev d);
-__global__ void ffd_hbm_kernel(KpDev d);
-__global__ void ffd_topo_hbm_kernel(KpDev d);
-__global__ void ffd_resv_hbm_kernel(KpDev d);
-__global__ void ffd_resv_topo_hbm_kernel(KpDev d);
-__global__ void ffd_pref_hbm_kernel(KpDev d);
-__global__ void ffd_pref_topo_hbm_kernel(KpDev d);
-__global__ void ffd_pref_resv_hbm_kernel(KpDev d);
-__global__ void ffd_pref_resv_topo_hbm_kernel(KpDev d);
+// each with its diagnostic twin <name>_prof (ffd_solve PROF), defined in kp_ffd_prof_*.hip
+#define KP_FFD_DECL(name)         \
+    __global__ void name(KpDev d); \
+    __global__ void name##_prof(KpDev d);
+KP_FFD_DECL(ffd_kernel)
+KP_FFD_DECL(ffd_topo_kernel)
+KP_FFD_DECL(ffd_resv_kernel)
+KP_FFD_DECL(ffd_resv_topo_kernel)
+KP_FFD_DECL(ffd_pref_kernel)
+KP_FFD_DECL(ffd_pref_topo_kernel)
+KP_FFD_DECL(ffd_pref_resv_kernel)
+KP_FFD_DECL(ffd_pref_resv_topo_kernel)
+KP_FFD_DECL(ffd_hbm_kernel)
+KP_FFD_DECL(ffd_topo_hbm_kernel)
+KP_FFD_DECL(ffd_resv_hbm_kernel)
+KP_FFD_DECL(ffd_resv_topo_hbm_kernel)
+KP_FFD_DECL(ffd_pref_hbm_kernel)
+KP_FFD_DECL(ffd_pref_topo_hbm_kernel)
+KP_FFD_DECL(ffd_pref_resv_hbm_kernel)
+KP_FFD_DECL(ffd_pref_resv_topo_hbm_kernel)
+#undef KP_FFD_DECL
+// [diagnostic twin][HBM * 8 + PREF * 4 + RESV * 2 + TOPO]
+typedef void (*FfdKernel)(KpDev);
+#define KP_FFD_ROW(sfx)                                                                                              \
+    {ffd_kernel##sfx,          ffd_topo_kernel##sfx,          ffd_resv_kernel##sfx,          ffd_resv_topo_kernel##sfx,      \
+     ffd_pref_kernel##sfx,     ffd_pref_topo_kernel##sfx,     ffd_pref_resv_kernel##sfx,     ffd_pref_resv_topo_kernel##sfx, \
+     ffd_hbm_kernel##sfx,      ffd_topo_hbm_kernel##sfx,      ffd_resv_hbm_kernel##sfx,      ffd_resv_topo_hbm_kernel##sfx,  \
+     ffd_pref_hbm_kernel##sfx, ffd_pref_topo_hbm_kernel##sfx, ffd_pref_resv_hbm_kernel##sfx, ffd_pref_resv_topo_hbm_kernel##sfx}
+static const FfdKernel kFfdKernels[2][16] = {KP_FFD_ROW(), KP_FFD_ROW(_prof)};
+#undef KP_FFD_ROW
 
 
 // ------------------------------------------------------------------------------------------------
@@ -442,17 +456,11 @@ hipError_t kp_launch_template_init(const KpDev& d, hipStream_t s) {
 // Per-device kernel attributes: called by kp_ctx_create with the ctx's device current (every ctx, so a second ctx on
 // another device of the same process gets them too; the call is idempotent and needs no process-wide flag).
 hipError_t kp_ffd_set_attributes() {
-    const void* ks[16] = {(const void*)ffd_kernel, (const void*)ffd_topo_kernel, (const void*)ffd_resv_kernel,
-                          (const void*)ffd_resv_topo_kernel, (const void*)ffd_pref_kernel, (const void*)ffd_pref_topo_kernel,
-                          (const void*)ffd_pref_resv_kernel, (const void*)ffd_pref_resv_topo_kernel,
-                          (const void*)ffd_hbm_kernel, (const void*)ffd_topo_hbm_kernel, (const void*)ffd_resv_hbm_kernel,
-                          (const void*)ffd_resv_topo_hbm_kernel, (const void*)ffd_pref_hbm_kernel,
-                          (const void*)ffd_pref_topo_hbm_kernel, (const void*)ffd_pref_resv_hbm_kernel,
-                          (const void*)ffd_pref_resv_topo_hbm_kernel};
-    for (const void* k : ks) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS_BYTES);
-        if (e != hipSuccess) return e;
-    }
+    for (const auto& row : kFfdKernels)
+        for (const FfdKernel k : row) {
+            const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS_BYTES);
+            if (e != hipSuccess) return e;
+        }
     return hipSuccess;
 }
 hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s) {
@@ -461,21 +469,10 @@ hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s) {
     // BestEffort minValues (PREF)
     const dim3 g(1), b((d.G > 0 ? KP_NWAVES_TOPO : KP_NWAVES) * 64);
     const bool pref = d.relax_next || d.best_effort;
-    if (d.slice_hbm) {
-        void (*k)(KpDev) = pref ? (d.ro ? (d.G > 0 ? ffd_pref_resv_topo_hbm_kernel : ffd_pref_resv_hbm_kernel)
-                                        : (d.G > 0 ? ffd_pref_topo_hbm_kernel : ffd_pref_hbm_kernel))
-                                : (d.ro ? (d.G > 0 ? ffd_resv_topo_hbm_kernel : ffd_resv_hbm_kernel)
-                                        : (d.G > 0 ? ffd_topo_hbm_kernel : ffd_hbm_kernel));
-        hipLaunchKernelGGL(k, g, b, bytes, s, d);
-    } else if (pref) {
-        if (d.ro && d.G > 0) hipLaunchKernelGGL(ffd_pref_resv_topo_kernel, g, b, bytes, s, d);
-        else if (d.ro) hipLaunchKernelGGL(ffd_pref_resv_kernel, g, b, bytes, s, d);
-        else if (d.G > 0) hipLaunchKernelGGL(ffd_pref_topo_kernel, g, b, bytes, s, d);
-        else hipLaunchKernelGGL(ffd_pref_kernel, g, b, bytes, s, d);
-    } else if (d.ro && d.G > 0) hipLaunchKernelGGL(ffd_resv_topo_kernel, g, b, bytes, s, d);
-    else if (d.ro) hipLaunchKernelGGL(ffd_resv_kernel, g, b, bytes, s, d);
-    else if (d.G > 0) hipLaunchKernelGGL(ffd_topo_kernel, g, b, bytes, s, d);
-    else hipLaunchKernelGGL(ffd_kernel, g, b, bytes, s, d);
+    // KPSIM_PROFILE / KPSIM_TRACE_POD: the diagnostic twin (the production kernels carry no stamps, n_* counters or trace)
+    const int twin = (d.profile || d.trace) ? 1 : 0;
+    const FfdKernel k = kFfdKernels[twin][(d.slice_hbm ? 8 : 0) + (pref ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)];
+    hipLaunchKernelGGL(k, g, b, bytes, s, d);
     return hipGetLastError();
 }
 hipError_t kp_launch_finalize(const KpDev& d, int n_nodeclaims, hipStream_t s) {

@@ -347,5 +347,12 @@ enum {
     // barrier that opens the slow path; the topology section (existing nodes, prefilter, scan, topology quick accept);
     // the class cache fill; the candidate evaluations; commit / templates / slice move / closing barrier; then the
     // iterations that end in a topology quick accept (count, cycles from the slow path's start to their end)
-    ST_SEG = 70, ST_TQ_ITERS = 75, ST_TQ_CYC = 76, ST_COUNT = 80
+    ST_SEG = 70, ST_TQ_ITERS = 75, ST_TQ_CYC = 76,
+    // KPSIM_PROFILE: wave 0's hand-off of a pod to the block, by part (cycles): fast-loop entry up to the first pop; the
+    // quick check that failed (merge_noop included); window flush + candidate collection; statistics write-back + the
+    // wait for the flushed request totals (ST_HANDOFF_WB: a free slot, so FfdShared and the LDS plan keep their size)
+    ST_HANDOFF = 77, ST_HANDOFF_WB = 43, ST_COUNT = 80
 };
+// The stage cycles (ST_CYC_*, ST_EV_REQ .. ST_EV_MIN, ST_SEG, ST_TQ_CYC, ST_HANDOFF), the ST_N_* counters and the
+// ST_TQ_WHY / ST_SLOW_WHY breakdowns are written by the diagnostic twins of the Solve kernels alone (ffd_solve PROF) and
+// read 0 otherwise; every other slot is exact in both.

@@ -16,7 +16,17 @@ NAMES = ["cyc_fast_loop", "cyc_sort", "cyc_slow_eval", "cyc_templates", "-", "cy
          "ev_off", "ev_types", "ev_min", "ev_calls", "quick_accepts", "slow_pods", "witness_misses", "cyc_q_pop",
          "cyc_q_scan", "cyc_q_check", "cyc_q_commit", "n_noinv", "n_winmove", "n_ldssort", "n_pivot", "n_winload",
          "n_flush", "n_shape", "n_lds_append", "n_lds_nowin", "n_lds_outside", "n_batches", "topo_quick",
-         "cyc_topo_setup", "cyc_topo_scan"]
+         "cyc_topo_setup", "cyc_topo_scan", "rej_requirements", "rej_topology", "rej_types", "rej_min_values",
+         # wave 0's hand-off of a pod to the block, by part (kp_layout.h ST_HANDOFF)
+         "cyc_ho_entry", "cyc_ho_failed_check", "cyc_ho_flush_collect", "cyc_ho_writeback"]
+
+
+def ffd_counters(ctx):
+    """kp_last_kernel_times [5..]: every FFD-kernel counter, the hand-off stamps past Context.ffd_cycles()'s 37 included."""
+    import ctypes as C
+    a = (C.c_double * (5 + len(NAMES)))()
+    ctx.check(ctx.L.kp_last_kernel_times(ctx.h, a, len(a)), "kp_last_kernel_times")
+    return list(a)[5:]
 
 
 def main():
@@ -37,7 +47,7 @@ def main():
     r = out.results()
     kt = ctx.kernel_times_ms()
     print(json.dumps({"config": which, "pods": n, "wall_ms": wall, "kernel_ms": kt, "nodeclaims": r.n_nodeclaims, "stats": r.stats,
-                      "ffd": dict(zip(NAMES, ctx.ffd_cycles()))}, indent=1))
+                      "ffd": dict(zip(NAMES, ffd_counters(ctx)))}, indent=1))
     ctx.close()
 
 
