@@ -30,27 +30,7 @@
 #include "kp_launch.h"
 #include "kp_layout.h"
 
-size_t kp_ffd_shared_bytes();
-size_t kp_ffd_shared_bytes_topo();
-bool kp_ffd_plan_lds(KpDev& d, int max_bytes);
-hipError_t kp_launch_class_mask(const KpDev& d, hipStream_t s);
-hipError_t kp_launch_template_init(const KpDev& d, hipStream_t s);
-hipError_t kp_launch_existing(const KpDev& d, hipStream_t s);
-hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s);
-hipError_t kp_ffd_set_attributes();
-hipError_t kp_cons_set_attributes();
-hipError_t kp_launch_finalize(const KpDev& d, int n_nodeclaims, hipStream_t s);
-bool kp_cons_plan_lds(const KpDev& d, KpCons& k, int max_bytes);
-hipError_t kp_launch_select_kernel(const KpLaunch& g, hipStream_t s);
-hipError_t kp_launch_consolidate(const KpDev& d, const KpCons& k, int n_workers, hipStream_t s, KpDev* d_dev,
-                                 KpCons* d_k);
-hipError_t kp_launch_cons_chunk_max(const KpDev& d, int64_t* cmax0, hipStream_t s);
-hipError_t kp_launch_multi_union(const KpCons& k, int nu, uint64_t* ubits, int32_t* rcand, int2* ulist, int32_t* ulen,
-                                 const int32_t* queue0, hipStream_t s);
-hipError_t kp_launch_cons_prep(const int32_t* queue0, int P, int32_t* rank, const int32_t* pending, int n_pending,
-                               uint64_t* pend_bits, hipStream_t s);
-hipError_t kp_queue_sort(const int64_t* fields, int n, int32_t* perm_a, int32_t* perm_b, uint64_t* keys_a,
-                         uint64_t* keys_b, void* temp, size_t* temp_bytes, hipStream_t s, int32_t** result);
+#include "kp_host.h"  // the kernel launchers' prototypes
 
 namespace {
 
@@ -118,19 +98,7 @@ const char* normalize_c(const char* k) {
         if (!strcmp(k, p.first)) return p.second;
     return k;
 }
-std::string normalize(const char* k) {
-    static const std::pair<const char*, const char*> m[] = {
-        {"failure-domain.beta.kubernetes.io/zone", "topology.kubernetes.io/zone"},
-        {"failure-domain.beta.kubernetes.io/region", "topology.kubernetes.io/region"},
-        {"beta.kubernetes.io/arch", "kubernetes.io/arch"},
-        {"beta.kubernetes.io/os", "kubernetes.io/os"},
-        {"beta.kubernetes.io/instance-type", "node.kubernetes.io/instance-type"},
-        {"topology.ebs.csi.aws.com/zone", "topology.kubernetes.io/zone"},
-    };
-    for (auto& p : m)
-        if (!strcmp(k, p.first)) return p.second;
-    return k;
-}
+std::string normalize(const char* k) { return normalize_c(k); }
 
 struct KeyDict {
     std::string name;
@@ -786,67 +754,73 @@ static hipError_t upload_resv(kp_ctx* c, hipStream_t s) {
     return c->d_ro_price.upload(pr, s);
 }
 
-static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint64_t epoch) try {
-    if (!ctx || !v) return KP_E_INVALID;
-    // every prepared solve / consolidation pass captured device pointers and sizes of the previous catalog, and the
-    // tables below may be reallocated: nothing prepared survives an upload, successful or not
-    ctx->have_catalog = false;
-    ctx->prepared = ctx->executed = false;
-    ctx->cons_prepared = ctx->cons_prep_valid = false;
-    ctx->cons_gen++;  // cached pass rows and read-backs of kp_consolidate_command are stale
-    HIPCHK(hipSetDevice(ctx->device));
-    const int T = v->n_types, R = v->n_resources, KL = v->n_label_keys;
-    if (T <= 0 || R <= 0 || R > KP_MAX_R) return fail(ctx, KP_E_INVALID, "bad n_types / n_resources");
-    if (T > KP_MAX_TYPES) return fail(ctx, KP_E_UNSUPPORTED, "more than KP_MAX_TYPES instance types");
-    kp_ctx* c = ctx;
-    c->have_catalog = false;
-    c->T = T;
-    c->TW = (T + 63) / 64;
-    c->R = R;
-    c->resource_names.assign(v->resource_names, v->resource_names + R);
-    c->type_names.assign(v->type_names, v->type_names + T);
-    c->cat = Dicts();
-    c->has_reserved = false;
-    c->solve_unsupported.clear();
+// Host-side tables of the catalog being uploaded: lives on catalog_upload_one's stack, filled stage by stage.
+struct CatEnc {
+    int Kc = 0;                                          // catalog keys: label keys, then offering keys
+    std::vector<int> lk, ok;                             // catalog key of each label key / offering key
+    std::vector<int8_t> st;                              // [T][Kc] KP_LABEL_* of (type, catalog key) ...
+    std::vector<std::vector<int>> tv;                    // ... and its value ids
+    std::vector<uint8_t> multi;                          // per catalog key: multi-valued
+    int kz = -1, kc = -1, kzi = -1, kri = -1, krt = -1;  // offering-key index of zone, capacity type, zone-id, reservation
+    std::vector<uint8_t> avail;                          // per offering row
+    std::vector<int> ro_rows;                            // the reserved offerings' rows
+    std::vector<uint16_t> tval;                          // device tables: single values, multi-value masks, DoesNotExist
+    std::vector<uint64_t> mmask, dne;
+};
+
+static kp_status cat_type_values(kp_ctx* ctx, const kp_catalog_view* v, CatEnc& ce) {
+    const int T = v->n_types, KL = v->n_label_keys;
     // label keys (type requirements) then offering keys
-    std::vector<int> lk(KL), ok(v->n_offering_keys);
-    for (int k = 0; k < KL; k++) lk[k] = c->cat.key(normalize(v->label_keys[k]));
-    for (int k = 0; k < v->n_offering_keys; k++) ok[k] = c->cat.key(normalize(v->offering_keys[k]));
-    const int Kc = (int)c->cat.keys.size();
-    c->Kcat = Kc;
+    ce.lk.resize(KL), ce.ok.resize(v->n_offering_keys);
+    for (int k = 0; k < KL; k++) ce.lk[k] = ctx->cat.key(normalize(v->label_keys[k]));
+    for (int k = 0; k < v->n_offering_keys; k++) ce.ok[k] = ctx->cat.key(normalize(v->offering_keys[k]));
+    const int Kc = ce.Kc = (int)ctx->cat.keys.size();
+    ctx->Kcat = Kc;
     // type values: state per (t, catalog key)
-    std::vector<int8_t> st((size_t)T * Kc, KP_LABEL_ABSENT);
-    std::vector<std::vector<int>> tv((size_t)T * Kc);
-    std::vector<uint8_t> multi(Kc, 0);
+    ce.st.assign((size_t)T * Kc, KP_LABEL_ABSENT);
+    ce.tv.assign((size_t)T * Kc, {});
+    ce.multi.assign(Kc, 0);
     for (int t = 0; t < T; t++) {
         for (int k = 0; k < KL; k++) {
             const int s = v->label_state[(size_t)t * KL + k];
-            const int key = lk[k];
-            auto& cell = tv[(size_t)t * Kc + key];
+            const int key = ce.lk[k];
+            auto& cell = ce.tv[(size_t)t * Kc + key];
             if (s == KP_LABEL_ABSENT) continue;
-            int8_t& stt = st[(size_t)t * Kc + key];
+            int8_t& stt = ce.st[(size_t)t * Kc + key];
             if (s == KP_LABEL_DOES_NOT_EXIST) {
                 if (stt == KP_LABEL_ABSENT) stt = KP_LABEL_DOES_NOT_EXIST;
                 continue;
             }
             const int o0 = v->label_offsets[(size_t)t * KL + k], o1 = v->label_offsets[(size_t)t * KL + k + 1];
             std::vector<int> ids;
-            for (int i = o0; i < o1; i++) ids.push_back(c->cat.keys[key].id(v->label_values[i]));
+            for (int i = o0; i < o1; i++) ids.push_back(ctx->cat.keys[key].id(v->label_values[i]));
             std::sort(ids.begin(), ids.end());
             ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
             cell = ids;
             stt = ids.empty() ? KP_LABEL_DOES_NOT_EXIST : KP_LABEL_IN;
-            if (ids.size() > 1) multi[key] = 1;
+            if (ids.size() > 1) ce.multi[key] = 1;
         }
     }
     // single-valued requirements of each type (Requirement.Len() == 1): instanceToNodeClaim's labels
-    c->type_single.assign(T, {});
+    ctx->type_single.assign(T, {});
     for (int t = 0; t < T; t++)
         for (int key = 0; key < Kc; key++)
-            if (tv[(size_t)t * Kc + key].size() == 1) c->type_single[t].push_back({key, tv[(size_t)t * Kc + key][0]});
+            if (ce.tv[(size_t)t * Kc + key].size() == 1) ctx->type_single[t].push_back({key, ce.tv[(size_t)t * Kc + key][0]});
     // offering-role keys are multi-valued on the type side in AWS (zone, capacity-type, ...): treat every key
     // that appears in offerings as multi so their value masks exist
-    for (int k = 0; k < v->n_offering_keys; k++) multi[ok[k]] = 1;
+    for (int k = 0; k < v->n_offering_keys; k++) ce.multi[ce.ok[k]] = 1;
+    return KP_OK;
+}
+
+// Offering o's label of offering key k (k < 0: the catalog has no such key): its state and value.
+static const char* offering_label(const kp_catalog_view* v, int o, int k, int& state) {
+    state = k < 0 ? KP_LABEL_ABSENT : v->offering_label_state[(size_t)o * v->n_offering_keys + k];
+    return k < 0 ? nullptr : v->offering_label_values[(size_t)o * v->n_offering_keys + k];
+}
+
+static kp_status cat_offering_values(kp_ctx* ctx, const kp_catalog_view* v, CatEnc& ce) {
+    kp_ctx* c = ctx;
+    const int T = v->n_types;
     // offering values
     const int O = v->n_offerings, KO = v->n_offering_keys;
     auto role = [&](const char* n) { return c->cat.find_key(n); };
@@ -856,53 +830,44 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
     c->key_resvid = role("karpenter.k8s.aws/capacity-reservation-id");
     c->key_resvtype = role("karpenter.k8s.aws/capacity-reservation-type");
     for (int k = 0; k < KO; k++) {
-        const int key = ok[k];
+        const int key = ce.ok[k];
         if (key != c->key_zone && key != c->key_ct && key != c->key_zoneid && key != c->key_resvid &&
             key != c->key_resvtype)
             return fail(ctx, KP_E_UNSUPPORTED, "offering requirement key outside {zone, capacity-type, zone-id, reservation}");
     }
     if (c->key_zone < 0 || c->key_ct < 0) return fail(ctx, KP_E_INVALID, "offerings need zone and capacity-type keys");
-    int kz = -1, kc = -1, kzi = -1, kri = -1, krt = -1;
     for (int k = 0; k < KO; k++) {
-        if (ok[k] == c->key_zone) kz = k;
-        if (ok[k] == c->key_ct) kc = k;
-        if (ok[k] == c->key_zoneid) kzi = k;
-        if (ok[k] == c->key_resvid) kri = k;
-        if (ok[k] == c->key_resvtype) krt = k;
+        if (ce.ok[k] == c->key_zone) ce.kz = k;
+        if (ce.ok[k] == c->key_ct) ce.kc = k;
+        if (ce.ok[k] == c->key_zoneid) ce.kzi = k;
+        if (ce.ok[k] == c->key_resvid) ce.kri = k;
+        if (ce.ok[k] == c->key_resvtype) ce.krt = k;
     }
     std::vector<int> zslots, cslots;  // value ids
     std::map<int, int> zone_to_zid;   // zone value id → zone-id value id or -1
     c->off_type.assign(O, 0);
     c->off_slot.assign(O, -1);
     std::vector<int> off_zone(O), off_ct(O);
-    std::vector<uint8_t> avail(O);
-    std::vector<int> ro_rows;
+    ce.avail.assign(O, 0);
     for (int o = 0; o < O; o++) {
         const int t = v->offering_type[o];
         if (t < 0 || t >= T) return fail(ctx, KP_E_INVALID, "offering_type out of range");
         c->off_type[o] = t;
-        avail[o] = v->offering_available[o] ? 1 : 0;
-        auto lab = [&](int k, int& state) -> const char* {
-            if (k < 0) {
-                state = KP_LABEL_ABSENT;
-                return nullptr;
-            }
-            state = v->offering_label_state[(size_t)o * KO + k];
-            return v->offering_label_values[(size_t)o * KO + k];
-        };
+        ce.avail[o] = v->offering_available[o] ? 1 : 0;
+        auto lab = [&](int k, int& state) { return offering_label(v, o, k, state); };
         int sz, sc, szi, sri, srt;
-        const char* z = lab(kz, sz);
-        const char* ct = lab(kc, sc);
-        const char* zi = lab(kzi, szi);
-        lab(kri, sri);
-        lab(krt, srt);
+        const char* z = lab(ce.kz, sz);
+        const char* ct = lab(ce.kc, sc);
+        const char* zi = lab(ce.kzi, szi);
+        lab(ce.kri, sri);
+        lab(ce.krt, srt);
         if (sz != KP_LABEL_IN || sc != KP_LABEL_IN) return fail(ctx, KP_E_UNSUPPORTED, "offering without zone / capacity-type");
         if (sri == KP_LABEL_IN || srt == KP_LABEL_IN || !strcmp(ct, "reserved")) {
             // reserved offerings (offering.go:164-194): the ResvTab of Solve and the launch tables; consolidation
             // rejects the catalog
             c->has_reserved = true;
             off_zone[o] = off_ct[o] = -1;
-            ro_rows.push_back(o);
+            ce.ro_rows.push_back(o);
             continue;
         }
         if (sri == KP_LABEL_ABSENT || srt == KP_LABEL_ABSENT)
@@ -942,7 +907,13 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
         c->slot_price[(size_t)c->off_type[o] * KP_MAX_SLOTS + s] = v->offering_price[o];
     }
     c->avail_zc.assign(T, 0);
-    rebuild_avail(c, avail);
+    rebuild_avail(c, ce.avail);
+    return KP_OK;
+}
+
+static kp_status cat_reserved_offerings(kp_ctx* ctx, const kp_catalog_view* v, CatEnc& ce) {
+    kp_ctx* c = ctx;
+    const int T = v->n_types;
     // reserved offerings: ResvTab rows ordered by type, each type's rows inside one 64-row word (padding rows between),
     // reservations numbered densely in row order; the ReservationManager's initial capacity per reservation
     // (NewReservationManager: the least ReservationCapacity among the offerings carrying the ID)
@@ -959,13 +930,13 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
     c->ro_price.clear();
     c->rcap0.clear();
     c->type_ro.assign(T, 0u);
-    if (!ro_rows.empty()) {
-        std::stable_sort(ro_rows.begin(), ro_rows.end(), [&](int a, int b) { return c->off_type[a] < c->off_type[b]; });
+    if (!ce.ro_rows.empty()) {
+        std::stable_sort(ce.ro_rows.begin(), ce.ro_rows.end(), [&](int a, int b) { return c->off_type[a] < c->off_type[b]; });
         std::map<int, int> rid_of;  // reservation-id value id -> reservation
-        for (size_t a = 0; a < ro_rows.size() && c->ro_ok;) {
+        for (size_t a = 0; a < ce.ro_rows.size() && c->ro_ok;) {
             size_t b = a;
-            while (b < ro_rows.size() && c->off_type[ro_rows[b]] == c->off_type[ro_rows[a]]) b++;
-            const int cnt = (int)(b - a), t = c->off_type[ro_rows[a]];
+            while (b < ce.ro_rows.size() && c->off_type[ce.ro_rows[b]] == c->off_type[ce.ro_rows[a]]) b++;
+            const int cnt = (int)(b - a), t = c->off_type[ce.ro_rows[a]];
             if (cnt > 64) {  // one instance type with more than 64 reservations: its rows do not fit one word
                 c->ro_ok = false;
                 c->ro_why = std::string("instance type ") + (v->type_names && v->type_names[t] ? v->type_names[t] : "?") +
@@ -985,17 +956,14 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
             const int first = (int)c->ro_type.size();
             c->type_ro[t] = (uint32_t)(first / 64) << 16 | (uint32_t)(first % 64) << 8 | (uint32_t)cnt;
             for (size_t i = a; i < b; i++) {
-                const int o = ro_rows[i];
-                auto lab = [&](int k, int& state) -> const char* {
-                    state = k < 0 ? KP_LABEL_ABSENT : v->offering_label_state[(size_t)o * KO + k];
-                    return k < 0 ? nullptr : v->offering_label_values[(size_t)o * KO + k];
-                };
+                const int o = ce.ro_rows[i];
+                auto lab = [&](int k, int& state) { return offering_label(v, o, k, state); };
                 int sz, sc, szi, sri, srt;
-                const char* z = lab(kz, sz);
-                const char* ct = lab(kc, sc);
-                const char* zi = lab(kzi, szi);
-                const char* ri = lab(kri, sri);
-                const char* rt = lab(krt, srt);
+                const char* z = lab(ce.kz, sz);
+                const char* ct = lab(ce.kc, sc);
+                const char* zi = lab(ce.kzi, szi);
+                const char* ri = lab(ce.kri, sri);
+                const char* rt = lab(ce.krt, srt);
                 if (strcmp(ct, "reserved") != 0 || sri != KP_LABEL_IN)
                     return fail(ctx, KP_E_UNSUPPORTED, "reserved offering without capacity-type reserved / reservation-id");
                 const int ridv = c->cat.keys[c->key_resvid].id(ri);
@@ -1036,7 +1004,13 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
     }
     c->ro_avail.assign(std::max<size_t>(1, (c->ro_type.size() + 63) / 64), 0ull);
     for (size_t i = 0; i < c->ro_off.size(); i++)
-        if (c->ro_off[i] >= 0 && avail[c->ro_off[i]]) c->ro_avail[i / 64] |= 1ull << (i % 64);
+        if (c->ro_off[i] >= 0 && ce.avail[c->ro_off[i]]) c->ro_avail[i / 64] |= 1ull << (i % 64);
+    return KP_OK;
+}
+
+static kp_status cat_value_masks(kp_ctx* ctx, const kp_catalog_view* v, CatEnc& ce) {
+    kp_ctx* c = ctx;
+    const int T = v->n_types, Kc = ce.Kc;
     // multi-valued keys: value masks (<= 64 values)
     c->wide_resvid = false;
     c->resvid_rows = false;
@@ -1045,9 +1019,9 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
     c->n_multi = 0;
     for (int k = 0; k < Kc; k++) {
         bool present = false;
-        for (int t = 0; t < T && !present; t++) present = st[(size_t)t * Kc + k] != KP_LABEL_ABSENT;
-        if (!present && !multi[k]) continue;  // offering-only key absent from every type
-        if (multi[k]) {
+        for (int t = 0; t < T && !present; t++) present = ce.st[(size_t)t * Kc + k] != KP_LABEL_ABSENT;
+        if (!present && !ce.multi[k]) continue;  // offering-only key absent from every type
+        if (ce.multi[k]) {
             if (c->cat.keys[k].vals.size() > 64) {
                 // the Solve tables hold a multi-valued label as a 64-bit value mask; the launch path has no such limit.
                 // The reservation-id label (one value per capacity reservation) is exempt: reserved offerings are
@@ -1063,9 +1037,9 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
                         const int r0 = (int)(tr >> 16) * 64 + (int)((tr >> 8) & 0xFF), n = (int)(tr & 0xFF);
                         std::set<int> rows;
                         for (int r = 0; r < n; r++) rows.insert(c->ro_ridv[r0 + r]);
-                        const int8_t ls = st[(size_t)t * Kc + k];
+                        const int8_t ls = ce.st[(size_t)t * Kc + k];
                         if (ls == KP_LABEL_IN) {
-                            const std::vector<int>& lv = tv[(size_t)t * Kc + k];
+                            const std::vector<int>& lv = ce.tv[(size_t)t * Kc + k];
                             rows_ok = std::set<int>(lv.begin(), lv.end()) == rows;
                         } else {
                             rows_ok = rows.empty();
@@ -1086,26 +1060,57 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
         }
     }
     const int TW = c->TW;
-    std::vector<uint16_t> tval((size_t)Kc * T, VAL_ABSENT);
-    std::vector<uint64_t> mmask((size_t)std::max(1, c->n_multi) * T, 0), dne((size_t)Kc * TW, 0);
+    ce.tval.assign((size_t)Kc * T, VAL_ABSENT);
+    ce.mmask.assign((size_t)std::max(1, c->n_multi) * T, 0), ce.dne.assign((size_t)Kc * TW, 0);
     c->h_multi_state.assign((size_t)std::max(1, c->n_multi) * T, KP_LABEL_ABSENT);
     for (int k = 0; k < Kc; k++) {
         for (int t = 0; t < T; t++) {
-            const int8_t s = st[(size_t)t * Kc + k];
-            if (s == KP_LABEL_DOES_NOT_EXIST) dne[(size_t)k * TW + t / 64] |= 1ull << (t % 64);
+            const int8_t s = ce.st[(size_t)t * Kc + k];
+            if (s == KP_LABEL_DOES_NOT_EXIST) ce.dne[(size_t)k * TW + t / 64] |= 1ull << (t % 64);
             if (c->cat_kflags[k] & KF_CAT_SINGLE) {
-                if (s == KP_LABEL_DOES_NOT_EXIST) tval[(size_t)k * T + t] = VAL_DNE;
-                else if (s == KP_LABEL_IN) tval[(size_t)k * T + t] = (uint16_t)tv[(size_t)t * Kc + k][0];
+                if (s == KP_LABEL_DOES_NOT_EXIST) ce.tval[(size_t)k * T + t] = VAL_DNE;
+                else if (s == KP_LABEL_IN) ce.tval[(size_t)k * T + t] = (uint16_t)ce.tv[(size_t)t * Kc + k][0];
                 if (c->cat.keys[k].vals.size() >= VAL_ABSENT) return fail(ctx, KP_E_UNSUPPORTED, "label dictionary too large");
             } else if (c->cat_kflags[k] & KF_CAT_MULTI) {
                 uint64_t m = 0;
                 if (s == KP_LABEL_IN)
-                    for (int id : tv[(size_t)t * Kc + k]) m |= 1ull << id;
-                mmask[(size_t)c->cat_multi[k] * T + t] = m;
+                    for (int id : ce.tv[(size_t)t * Kc + k]) m |= 1ull << id;
+                ce.mmask[(size_t)c->cat_multi[k] * T + t] = m;
                 c->h_multi_state[(size_t)c->cat_multi[k] * T + t] = (uint8_t)s;
             }
         }
     }
+    return KP_OK;
+}
+
+static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint64_t epoch) try {
+    if (!ctx || !v) return KP_E_INVALID;
+    // every prepared solve / consolidation pass captured device pointers and sizes of the previous catalog, and the
+    // tables below may be reallocated: nothing prepared survives an upload, successful or not
+    ctx->have_catalog = false;
+    ctx->prepared = ctx->executed = false;
+    ctx->cons_prepared = ctx->cons_prep_valid = false;
+    ctx->cons_gen++;  // cached pass rows and read-backs of kp_consolidate_command are stale
+    HIPCHK(hipSetDevice(ctx->device));
+    const int T = v->n_types, R = v->n_resources;
+    if (T <= 0 || R <= 0 || R > KP_MAX_R) return fail(ctx, KP_E_INVALID, "bad n_types / n_resources");
+    if (T > KP_MAX_TYPES) return fail(ctx, KP_E_UNSUPPORTED, "more than KP_MAX_TYPES instance types");
+    kp_ctx* c = ctx;
+    c->have_catalog = false;
+    c->T = T;
+    c->TW = (T + 63) / 64;
+    c->R = R;
+    c->resource_names.assign(v->resource_names, v->resource_names + R);
+    c->type_names.assign(v->type_names, v->type_names + T);
+    c->cat = Dicts();
+    c->has_reserved = false;
+    c->solve_unsupported.clear();
+    CatEnc ce;
+    for (auto stage : {cat_type_values, cat_offering_values, cat_reserved_offerings, cat_value_masks}) {
+        const kp_status st = stage(ctx, v, ce);
+        if (st != KP_OK) return st;
+    }
+    const int TW = c->TW, Kc = ce.Kc;
     c->alloc_rt.assign((size_t)R * T, 0);
     c->cap_rt.assign((size_t)R * T, 0);
     std::vector<uint64_t> nonneg(TW, 0);
@@ -1125,19 +1130,19 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
     for (int i = 0; i < T; i++) {
         rank[idx[i]] = (i > 0 && c->type_names[idx[i]] == c->type_names[idx[i - 1]]) ? rank[idx[i - 1]] : (uint32_t)i;
     }
-    c->h_multi_mask = mmask;
+    c->h_multi_mask = ce.mmask;
     hipStream_t s = c->stream;
-    HIPCHK(c->d_type_val.upload(tval, s));
-    HIPCHK(c->d_multi_mask.upload(mmask, s));
+    HIPCHK(c->d_type_val.upload(ce.tval, s));
+    HIPCHK(c->d_multi_mask.upload(ce.mmask, s));
     c->multi16_ok = c->n_multi <= 5;
     for (int k = 0; k < Kc; k++)
         if ((c->cat_kflags[k] & KF_CAT_MULTI) && c->cat.keys[k].vals.size() > 16) c->multi16_ok = false;
     if (c->multi16_ok) {
-        std::vector<uint16_t> m16(mmask.size());
-        for (size_t i = 0; i < mmask.size(); i++) m16[i] = (uint16_t)mmask[i];
+        std::vector<uint16_t> m16(ce.mmask.size());
+        for (size_t i = 0; i < ce.mmask.size(); i++) m16[i] = (uint16_t)ce.mmask[i];
         HIPCHK(c->d_multi16.upload(m16, s));
     }
-    HIPCHK(c->d_dne_mask.upload(dne, s));
+    HIPCHK(c->d_dne_mask.upload(ce.dne, s));
     HIPCHK(c->d_alloc.upload(c->alloc_rt, s));
     HIPCHK(c->d_cap.upload(c->cap_rt, s));
     HIPCHK(c->d_avail_zc.upload(c->avail_zc, s));
@@ -1149,7 +1154,7 @@ static kp_status catalog_upload_one(kp_ctx* ctx, const kp_catalog_view* v, uint6
     HIPCHK(c->d_nonneg.upload(nonneg, s));
     HIPCHK(upload_resv(c, s));
     {
-        kp_status lst = upload_launch_tables(c, v, avail);
+        kp_status lst = upload_launch_tables(c, v, ce.avail);
         if (lst != KP_OK) return lst;
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -1561,31 +1566,17 @@ static uint64_t late_birth(const std::vector<uint64_t>& sib, uint64_t born, uint
     return born;
 }
 
-// Topology groups ([core] scheduling/topology.go Update / updateInverseAntiAffinity, topologygroup.go Hash): Go keeps
-// one group per TopologyGroup.Hash() — topology key, type, namespaces, label selector, maxSkew and the node filter
-// (MakeTopologyNodeFilter: the requirement key sets of the nodeSelector with each required term, the policies, the
-// tolerations); hashstructure skips unexported fields, so requirement values and minDomains are not part of it.  Here
-// every (class, term) of one identity is one group owned by all those classes, with the first owner's node filter,
-// minDomains and selector (see the owner choice below).  A group is created by NewTopology when a pod that owns it is in the batch, or by Topology.Update when a pod relaxes
-// into a spec that owns it (countDomains then counts only the bound pods): an identity that only a relaxed stage can
-// own — its other owners do not include that stage's input class — is "late", born on the device when the first pod
-// relaxes into an owner (at most 64 such identities).  Interns the topology keys.
-static kp_status topo_build(kp_ctx* c, const kp_solve_input* in, const std::vector<std::map<int, HReq>>& creq,
-                            const std::vector<std::vector<std::map<int, HReq>>>& cfilt, TopoHost& th, std::string& err) {
+struct TEnt {  // one (class, term[, inverse]) owner of an identity
+    int cls = 0;
+    std::string sig;  // the semantics Hash() does not see: selection, minDomains, Honor filter values / tolerations
+    HGroup g;
+};
+// The (class, term[, inverse]) owners of every TopologyGroup.Hash() identity, in class order (topo_build's first pass).
+static kp_status topo_entries(kp_ctx* c, const kp_solve_input* in, const std::vector<std::vector<std::map<int, HReq>>>& cfilt,
+                              std::vector<TEnt>& ents, std::vector<std::vector<int>>& by_ident,
+                              std::map<std::string, int>& idents, std::string& err) {
     const int C = in->n_classes;
     const PrefExpansion& X = c->pref;
-    th = TopoHost();
-    th.cons.assign(C, {});
-    th.rec.assign(C, {});
-    th.neutral.assign(C, {});
-    struct TEnt {  // one (class, term[, inverse]) owner of an identity
-        int cls = 0;
-        std::string sig;  // the semantics Hash() does not see: selection, minDomains, Honor filter values / tolerations
-        HGroup g;
-    };
-    std::vector<TEnt> ents;
-    std::vector<std::vector<int>> by_ident;  // identity → its entries, class order
-    std::map<std::string, int> idents;       // identity → index
     auto hreq_str = [](const HReq& q) {
         std::string r = std::to_string(q.key) + (q.complement ? "!" : "=");
         for (int v : q.vals) r += std::to_string(v) + ",";
@@ -1712,6 +1703,31 @@ static kp_status topo_build(kp_ctx* c, const kp_solve_input* in, const std::vect
             }
         }
     }
+    return KP_OK;
+}
+
+// Topology groups ([core] scheduling/topology.go Update / updateInverseAntiAffinity, topologygroup.go Hash): Go keeps
+// one group per TopologyGroup.Hash() — topology key, type, namespaces, label selector, maxSkew and the node filter
+// (MakeTopologyNodeFilter: the requirement key sets of the nodeSelector with each required term, the policies, the
+// tolerations); hashstructure skips unexported fields, so requirement values and minDomains are not part of it.  Here
+// every (class, term) of one identity is one group owned by all those classes, with the first owner's node filter,
+// minDomains and selector (see the owner choice below).  A group is created by NewTopology when a pod that owns it is in the batch, or by Topology.Update when a pod relaxes
+// into a spec that owns it (countDomains then counts only the bound pods): an identity that only a relaxed stage can
+// own — its other owners do not include that stage's input class — is "late", born on the device when the first pod
+// relaxes into an owner (at most 64 such identities).  Interns the topology keys.
+static kp_status topo_build(kp_ctx* c, const kp_solve_input* in, const std::vector<std::map<int, HReq>>& creq,
+                            const std::vector<std::vector<std::map<int, HReq>>>& cfilt, TopoHost& th, std::string& err) {
+    const int C = in->n_classes;
+    const PrefExpansion& X = c->pref;
+    th = TopoHost();
+    th.cons.assign(C, {});
+    th.rec.assign(C, {});
+    th.neutral.assign(C, {});
+    std::vector<TEnt> ents;
+    std::vector<std::vector<int>> by_ident;  // identity → its entries, class order
+    std::map<std::string, int> idents;       // identity → index
+    const kp_status es = topo_entries(c, in, cfilt, ents, by_ident, idents, err);
+    if (es != KP_OK) return es;
     if (ents.empty()) return KP_OK;
     const int NI = (int)idents.size();
     const int C0 = X.n_input;
@@ -1954,122 +1970,152 @@ static thread_local std::chrono::steady_clock::time_point g_prep_t;
             g_prep_t = _n;                                                                                    \
         }                                                                                                     \
     } while (0)
-extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try {
-    g_prep_t = std::chrono::steady_clock::now();
-    if (!ctx || !in) return KP_E_INVALID;
-    ctx->cons_prep_valid = false;
-    ctx->cons_gen++;  // cached pass rows and read-backs of kp_consolidate_command are stale
-    if (!ctx->have_catalog) return fail(ctx, KP_E_STATE, "kp_solve before kp_catalog_upload");
-    if (!ctx->solve_unsupported.empty()) return fail(ctx, KP_E_UNSUPPORTED, "Solve: " + ctx->solve_unsupported);
-    if (ctx->has_reserved && !ctx->ro_ok)
-        return fail(ctx, KP_E_UNSUPPORTED, "Solve over this catalog: " + ctx->ro_why);
-    const auto t0 = clk::now();
-    HIPCHK(hipSetDevice(ctx->device));
-    kp_ctx* c = ctx;
-    c->prepared = c->executed = false;
-    c->cons_prepared = false;
-    c->any_min_values = false;
-    c->max_min_values = 0;
-    c->min_multi = false;
+// Host-side tables of the solve being prepared: lives on kp_solve_prepare's stack, filled stage by stage.
+struct SolveEnc {
+    std::vector<std::map<int, HReq>> creq, cstrict, treq;  // per class, its strict requirements (podDomains), per template
+    std::vector<std::vector<std::map<int, HReq>>> cfilt;   // per class: the Honor spreads' node-filter rows
+    std::vector<int> npo;                                  // template -> input NodePool
+    TopoHost th;
+    int E = 0, EW = 0, NT = 0, CT = 0, K = 0, DW = 0, NCcap = 0, M = 0, hostname_key = -1;
+    std::vector<std::vector<std::pair<int, int>>> exlab;   // (key, value id) per existing node
+    std::map<int, int> host_node;                          // hostname value id -> existing node
+    // key layout
+    std::vector<uint32_t> kflags;
+    std::vector<int32_t> kcat, kmulti, woff, nw, nval, vbase;
+    std::vector<uint8_t> isint;
+    std::vector<int64_t> ival;
+    // class digests: pod classes, templates, then the filter rows
+    std::vector<ReqHdr> chdr;
+    std::vector<uint64_t> cwords;
+    std::vector<uint32_t> cflags;
+    std::vector<int32_t> koff, ckeys, cwsoff, min_keys, xkoff, xkeys;
+    std::vector<uint8_t> ckneu, hblock;  // ckneu: parallel to ckeys, key added for topology narrowing only
+    std::vector<int2> frow;
+    bool mayfix = false;
+    // template, existing-node and pod tables
+    std::vector<uint64_t> tol, rows, exw, extol;
+    std::vector<int64_t> daemon, remaining, exav, exrq;
+    std::vector<uint8_t> limit_set;
+    std::vector<ReqHdr> exhdr;
+    std::vector<int32_t> shape_next;
+};
+
+static kp_status solve_expand(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    ctx->any_min_values = false;
+    ctx->max_min_values = 0;
+    ctx->min_multi = false;
     if (in->min_values_policy != KP_MIN_VALUES_STRICT && in->min_values_policy != KP_MIN_VALUES_BEST_EFFORT)
         return fail(ctx, KP_E_INVALID, "unknown MIN_VALUES_POLICY");
-    c->best_effort = in->min_values_policy == KP_MIN_VALUES_BEST_EFFORT;
+    ctx->best_effort = in->min_values_policy == KP_MIN_VALUES_BEST_EFFORT;
     if (in->n_classes < 0 || (in->n_classes > 0 && !in->classes)) return fail(ctx, KP_E_INVALID, "pod classes");
     for (int i = 0; i < in->pods.n_pods; i++)
         if (in->pods.class_id[i] < 0 || in->pods.class_id[i] >= in->n_classes)
             return fail(ctx, KP_E_INVALID, "pod class out of range");
     {
         std::string perr;
-        kp_status pst = expand_preferences(in, c->pref_policy, c->pref, perr);
+        kp_status pst = expand_preferences(in, ctx->pref_policy, ctx->pref, perr);
         if (pst != KP_OK) return fail(ctx, pst, perr);
     }
-    in = &c->pref.in;  // from here on: the expanded classes (stage 0 of input class i is class i)
-    const int T = c->T, TW = c->TW, R = c->R, P = in->pods.n_pods, C = in->n_classes;
-    PREP_MARK(0);
+    return KP_OK;
+}
+
+static kp_status solve_class_reqs(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int C = in->n_classes;
     // ---- dictionaries: catalog ∪ solve strings ----
-    c->sol = c->cat;
-    std::vector<std::map<int, HReq>> creq(C);
+    ctx->sol = ctx->cat;
+    se.creq.assign(C, {});
     std::string err;
     for (int i = 0; i < C; i++)
-        if (!build_hreqs(c, in->classes[i].requirements, in->classes[i].n_requirements, creq[i], err)) return fail(ctx, KP_E_INVALID, err);
+        if (!build_hreqs(ctx, in->classes[i].requirements, in->classes[i].n_requirements, se.creq[i], err)) return fail(ctx, KP_E_INVALID, err);
     // spread node filters of classes with a nodeAffinityPolicy Honor spread, and strict requirements (podDomains) of
     // classes whose requirements carry a preferred node-affinity term (expand_preferences)
-    std::vector<std::vector<std::map<int, HReq>>> cfilt(C);
-    std::vector<std::map<int, HReq>> cstrict(C);
+    se.cfilt.assign(C, {});
+    se.cstrict.assign(C, {});
     for (int i = 0; i < C; i++) {
         bool honor = false;
         for (int q = 0; q < in->classes[i].n_topology; q++)
             honor |= in->classes[i].topology[q].type == KP_TOPO_SPREAD &&
                      in->classes[i].topology[q].node_affinity_policy == KP_POLICY_HONOR;
-        if (honor && c->pref.filt[i].size() > 64)
+        if (honor && ctx->pref.filt[i].size() > 64)
             return fail(ctx, KP_E_UNSUPPORTED, "a nodeAffinityPolicy Honor spread with more than 64 node-filter terms");
         if (honor)
-            for (auto& f : c->pref.filt[i]) {
-                cfilt[i].emplace_back();
-                if (!build_hreqs(c, f.data(), (int)f.size(), cfilt[i].back(), err)) return fail(ctx, KP_E_INVALID, err);
+            for (auto& f : ctx->pref.filt[i]) {
+                se.cfilt[i].emplace_back();
+                if (!build_hreqs(ctx, f.data(), (int)f.size(), se.cfilt[i].back(), err)) return fail(ctx, KP_E_INVALID, err);
             }
-        if (c->pref.has_strict[i] &&
-            !build_hreqs(c, c->pref.strict[i].data(), (int)c->pref.strict[i].size(), cstrict[i], err))
+        if (ctx->pref.has_strict[i] &&
+            !build_hreqs(ctx, ctx->pref.strict[i].data(), (int)ctx->pref.strict[i].size(), se.cstrict[i], err))
             return fail(ctx, KP_E_INVALID, err);
     }
+    return KP_OK;
+}
+
+static kp_status solve_templates(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int C = in->n_classes;
+    std::string err;
     // templates: NodePools ordered by weight desc, name asc ([core] NodePoolList.OrderByWeight)
-    std::vector<int> npo(in->n_nodepools);
-    for (int i = 0; i < in->n_nodepools; i++) npo[i] = i;
-    std::sort(npo.begin(), npo.end(), [&](int a, int b) {
+    se.npo.resize(in->n_nodepools);
+    for (int i = 0; i < in->n_nodepools; i++) se.npo[i] = i;
+    std::sort(se.npo.begin(), se.npo.end(), [&](int a, int b) {
         if (in->nodepools[a].weight != in->nodepools[b].weight) return in->nodepools[a].weight > in->nodepools[b].weight;
         return strcmp(in->nodepools[a].name, in->nodepools[b].name) < 0;
     });
-    const int NT = (int)npo.size();
+    const int NT = se.NT = (int)se.npo.size();
     if (NT > KP_MAX_NP) return fail(ctx, KP_E_UNSUPPORTED, "more than 63 NodePools");
     if (C + NT >= 65535) return fail(ctx, KP_E_UNSUPPORTED, "too many pod classes");
-    std::vector<std::map<int, HReq>> treq(NT);
+    se.treq.assign(NT, {});
     for (int j = 0; j < NT; j++) {
-        const kp_nodepool& np = in->nodepools[npo[j]];
-        if (!build_hreqs(c, np.requirements, np.n_requirements, treq[j], err)) return fail(ctx, KP_E_INVALID, err);
+        const kp_nodepool& np = in->nodepools[se.npo[j]];
+        if (!build_hreqs(ctx, np.requirements, np.n_requirements, se.treq[j], err)) return fail(ctx, KP_E_INVALID, err);
     }
     for (int i = 0; i < C; i++)
-        for (auto& kv : creq[i])
+        for (auto& kv : se.creq[i])
             if (kv.second.has_min) return fail(ctx, KP_E_INVALID, "pod requirements cannot carry minValues");
-    if (c->wide_resvid) {  // see catalog_upload_one: no per-type value masks for a reservation-id label this wide
-        for (int i = 0; i < C && !c->resvid_rows; i++)
-            if (creq[i].count(c->key_resvid))
+    if (ctx->wide_resvid) {  // see catalog_upload_one: no per-type value masks for a reservation-id label this wide
+        for (int i = 0; i < C && !ctx->resvid_rows; i++)
+            if (se.creq[i].count(ctx->key_resvid))
                 return fail(ctx, KP_E_UNSUPPORTED, "a pod requirement on capacity-reservation-id over more than 64 reservations "
                                                    "whose labels are not the types' reserved offerings");
         for (int j = 0; j < NT; j++) {
-            auto it = treq[j].find(c->key_resvid);
-            if (it == treq[j].end()) continue;
-            if (!c->resvid_rows)
+            auto it = se.treq[j].find(ctx->key_resvid);
+            if (it == se.treq[j].end()) continue;
+            if (!ctx->resvid_rows)
                 return fail(ctx, KP_E_UNSUPPORTED, "a NodePool requirement on capacity-reservation-id over more than 64 "
                                                    "reservations whose labels are not the types' reserved offerings");
             if (it->second.has_min)  // minValues counts distinct values per type through 64-bit masks
                 return fail(ctx, KP_E_UNSUPPORTED, "minValues on capacity-reservation-id over more than 64 reservations");
         }
     }
-    TopoHost th;
-    {
-        const kp_status ts = topo_build(c, in, creq, cfilt, th, err);
-        if (ts != KP_OK) return fail(ctx, ts, err);
-    }
+    return KP_OK;
+}
+
+static kp_status solve_topology_groups(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    std::string err;
+    const kp_status ts = topo_build(ctx, in, se.creq, se.cfilt, se.th, err);
+    return ts != KP_OK ? fail(ctx, ts, err) : KP_OK;
+}
+
+static kp_status solve_existing(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int C = in->n_classes;
     // existing nodes (ExistingNode, [core] scheduling/existingnode.go NewExistingNode): requirements =
     // NewLabelRequirements(node labels) + hostname In [name].  Only label keys some pod class constrains can
     // influence Compatible (it iterates the pod's keys), so only those are interned.
-    const int E = in->n_existing;
-    const int hostname_key = c->sol.find_key("kubernetes.io/hostname");
-    std::vector<std::vector<std::pair<int, int>>> exlab(E);  // (key, value id) per node
+    const int E = se.E = in->n_existing;
+    const int hostname_key = se.hostname_key = ctx->sol.find_key("kubernetes.io/hostname");
+    se.exlab.assign(E, {});  // (key, value id) per node
     for (int j = 0; j < E; j++) {
         const kp_existing_node& en = in->existing[j];
         if (!en.available) return fail(ctx, KP_E_INVALID, "existing node without available resources");
         for (int l = 0; l < en.n_labels; l++) {
-            const int k = c->sol.find_key(normalize(en.label_keys[l]));
+            const int k = ctx->sol.find_key(normalize(en.label_keys[l]));
             if (k < 0 || k == hostname_key) continue;
-            exlab[j].push_back({k, c->sol.keys[k].id(en.label_values[l] ? en.label_values[l] : "")});
+            se.exlab[j].push_back({k, ctx->sol.keys[k].id(en.label_values[l] ? en.label_values[l] : "")});
         }
-        if (hostname_key >= 0) exlab[j].push_back({hostname_key, c->sol.keys[hostname_key].id(en.name ? en.name : "")});
+        if (hostname_key >= 0) se.exlab[j].push_back({hostname_key, ctx->sol.keys[hostname_key].id(en.name ? en.name : "")});
     }
-    std::map<int, int> host_node;  // hostname value id → existing node
     if (hostname_key >= 0)
-        for (int j = E - 1; j >= 0; j--) host_node[exlab[j].back().second] = j;
-    const int K = (int)c->sol.keys.size();
+        for (int j = E - 1; j >= 0; j--) se.host_node[se.exlab[j].back().second] = j;
+    const int K = se.K = (int)ctx->sol.keys.size();
     if (K > KP_MAX_KEYS) return fail(ctx, KP_E_UNSUPPORTED, "too many label keys");
     // ExistingNode.Add's requirement merge only changes a node when a NotIn / DoesNotExist pod requirement meets a key
     // the node lacks (a node's labels are single values, which a compatible merge leaves as they are), and that change
@@ -2081,79 +2127,85 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     {
         std::vector<uint8_t> neg(K, 0), pos(K, 0), undef(K, 0), topo(K, 0);
         for (int i = 0; i < C; i++)
-            for (auto& kv : creq[i]) {
+            for (auto& kv : se.creq[i]) {
                 const HReq& q = kv.second;
                 const bool ng = (q.complement && !q.vals.empty()) || (!q.complement && q.vals.empty());
                 (ng ? neg : pos)[kv.first] = 1;
             }
-        for (const HGroup& g : th.g) topo[g.key] = 1;
+        for (const HGroup& g : se.th.g) topo[g.key] = 1;
         std::vector<uint8_t> has(K, 0);
         for (int j = 0; j < E; j++) {
-            for (auto& kv : exlab[j]) has[kv.first] = 1;
+            for (auto& kv : se.exlab[j]) has[kv.first] = 1;
             for (int k = 0; k < K; k++) {
                 if (!has[k]) undef[k] = 1;
             }
-            for (auto& kv : exlab[j]) has[kv.first] = 0;
+            for (auto& kv : se.exlab[j]) has[kv.first] = 0;
         }
-        c->cons_mutcls.assign(C, 0);
+        ctx->cons_mutcls.assign(C, 0);
         for (int i = 0; i < C; i++)
-            for (auto& kv : creq[i]) {
+            for (auto& kv : se.creq[i]) {
                 const HReq& q = kv.second;
                 const int k = kv.first;
                 const bool ng = (q.complement && !q.vals.empty()) || (!q.complement && q.vals.empty());
-                if (ng && undef[k] && (pos[k] || topo[k])) c->cons_mutcls[i] = 1;
+                if (ng && undef[k] && (pos[k] || topo[k])) ctx->cons_mutcls[i] = 1;
             }
     }
+    return KP_OK;
+}
+
+static kp_status solve_key_layout(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int K = se.K;
     // ---- key layout ----
-    std::vector<uint32_t> kflags(K, 0);
-    std::vector<int32_t> kcat(K, -1), kmulti(K, -1), woff(K), nw(K), nval(K), vbase(K);
-    std::vector<uint8_t> isint;
-    std::vector<int64_t> ival;
-    int DW = 0;
+    se.kflags.assign(K, 0);
+    se.kcat.assign(K, -1), se.kmulti.assign(K, -1);
+    se.woff.resize(K), se.nw.resize(K), se.nval.resize(K), se.vbase.resize(K);
+    int& DW = se.DW;
     for (int k = 0; k < K; k++) {
-        const KeyDict& kd = c->sol.keys[k];
-        if (well_known(kd.name)) kflags[k] |= KF_WELL_KNOWN;
-        if (k < c->Kcat && c->cat_kflags[k]) {
-            kflags[k] |= c->cat_kflags[k];
-            kcat[k] = k;
-            kmulti[k] = c->cat_multi[k];
-        } else if (k == c->key_resvid && c->resvid_rows) {  // values per type: its ResvTab rows (DoesNotExist: dne_mask)
-            kflags[k] |= KF_RESV_ROWS;
-            kcat[k] = k;
+        const KeyDict& kd = ctx->sol.keys[k];
+        if (well_known(kd.name)) se.kflags[k] |= KF_WELL_KNOWN;
+        if (k < ctx->Kcat && ctx->cat_kflags[k]) {
+            se.kflags[k] |= ctx->cat_kflags[k];
+            se.kcat[k] = k;
+            se.kmulti[k] = ctx->cat_multi[k];
+        } else if (k == ctx->key_resvid && ctx->resvid_rows) {  // values per type: its ResvTab rows (DoesNotExist: dne_mask)
+            se.kflags[k] |= KF_RESV_ROWS;
+            se.kcat[k] = k;
         }
-        nval[k] = (int)kd.vals.size();
-        nw[k] = std::max(1, (nval[k] + 63) / 64);
-        woff[k] = DW;
-        DW += nw[k];
-        vbase[k] = (int)isint.size();
+        se.nval[k] = (int)kd.vals.size();
+        se.nw[k] = std::max(1, (se.nval[k] + 63) / 64);
+        se.woff[k] = DW;
+        DW += se.nw[k];
+        se.vbase[k] = (int)se.isint.size();
         for (auto& s : kd.vals) {
             int64_t x = 0;
-            isint.push_back(go_atoi(s.c_str(), x) ? 1 : 0);
-            ival.push_back(x);
+            se.isint.push_back(go_atoi(s.c_str(), x) ? 1 : 0);
+            se.ival.push_back(x);
         }
-        if ((kflags[k] & KF_CAT_MULTI) && nval[k] > 64)
+        if ((se.kflags[k] & KF_CAT_MULTI) && se.nval[k] > 64)
             return fail(ctx, KP_E_UNSUPPORTED, "multi-valued label with > 64 values after adding pod values");
     }
     // topology keys the device narrows per value: multi-valued catalog labels (zone, capacity-type, zone-id, ...) and
     // labels no instance type carries, each with at most 64 values; hostname is handled per host
-    for (const HGroup& g : th.g) {
+    for (const HGroup& g : se.th.g) {
         if (g.host) continue;
-        if ((kflags[g.key] & KF_CAT_SINGLE) || nval[g.key] > 64)
-            return fail(ctx, KP_E_UNSUPPORTED, "topology key " + c->sol.keys[g.key].name +
+        if ((se.kflags[g.key] & KF_CAT_SINGLE) || se.nval[g.key] > 64)
+            return fail(ctx, KP_E_UNSUPPORTED, "topology key " + ctx->sol.keys[g.key].name +
                                                    ": single-valued instance-type labels or > 64 values are not supported");
     }
-    PREP_MARK(1);
+    return KP_OK;
+}
+
+static kp_status solve_digests(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int C = in->n_classes, NT = se.NT, K = se.K, DW = se.DW, hostname_key = se.hostname_key;
     // ---- class digests: pod classes then templates ----
-    const int CT = C + NT;
-    std::vector<ReqHdr> chdr((size_t)CT * K);
-    std::vector<uint64_t> cwords((size_t)CT * DW, 0);
-    std::vector<int32_t> koff(CT + 1, 0), ckeys, cwsoff;
-    std::vector<uint8_t> ckneu;  // parallel to ckeys: key added for topology narrowing only
-    std::vector<uint32_t> cflags(CT, 0);
-    std::vector<int32_t> min_keys((size_t)NT * KP_MAX_CLASS_KEYS, -1);
-    std::vector<int32_t> xkoff(C + 1, 0), xkeys;
-    std::vector<uint8_t> hblock(std::max(C, 1), 0);
-    bool mayfix = false;
+    const int CT = se.CT = C + NT;
+    se.chdr.resize((size_t)CT * K);
+    se.cwords.assign((size_t)CT * DW, 0);
+    se.koff.assign(CT + 1, 0);
+    se.cflags.assign(CT, 0);
+    se.min_keys.assign((size_t)NT * KP_MAX_CLASS_KEYS, -1);
+    se.xkoff.assign(C + 1, 0);
+    se.hblock.assign(std::max(C, 1), 0);
     auto encode = [&](int row, const std::map<int, HReq>& rq) -> bool {
         int so = 0, nk = 0;
         for (auto& kv : rq) {
@@ -2164,179 +2216,193 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
             h.minv = q.minv;
             h.gt = q.gt;
             h.lt = q.lt;
-            chdr[(size_t)row * K + q.key] = h;
-            for (int vv : q.vals) cwords[(size_t)row * DW + woff[q.key] + vv / 64] |= 1ull << (vv % 64);
+            se.chdr[(size_t)row * K + q.key] = h;
+            for (int vv : q.vals) se.cwords[(size_t)row * DW + se.woff[q.key] + vv / 64] |= 1ull << (vv % 64);
             if (row < C) {
-                xkeys.push_back(q.key);
-                if ((q.complement && !q.vals.empty()) || (!q.complement && q.vals.empty())) mayfix = true;  // NotIn / DNE
+                se.xkeys.push_back(q.key);
+                if ((q.complement && !q.vals.empty()) || (!q.complement && q.vals.empty())) se.mayfix = true;  // NotIn / DNE
                 if (q.key == hostname_key) {
                     // every new NodeClaim carries hostname In [a fresh placeholder]: only NotIn / Exists (no bounds)
                     // intersect it; the merged value stays the placeholder and is dropped at FinalizeScheduling
-                    if (!(q.complement && !q.has_gt && !q.has_lt)) hblock[row] = 1;
+                    if (!(q.complement && !q.has_gt && !q.has_lt)) se.hblock[row] = 1;
                     continue;
                 }
             }
             nk++;
-            ckeys.push_back(q.key);
-            ckneu.push_back(0);
-            cwsoff.push_back(so);
-            so += nw[q.key];
-            if (q.key == c->key_zone || q.key == c->key_ct || q.key == c->key_zoneid || q.key == c->key_resvid ||
-                q.key == c->key_resvtype)
-                cflags[row] |= CF_OFFERING;
+            se.ckeys.push_back(q.key);
+            se.ckneu.push_back(0);
+            se.cwsoff.push_back(so);
+            so += se.nw[q.key];
+            if (q.key == ctx->key_zone || q.key == ctx->key_ct || q.key == ctx->key_zoneid || q.key == ctx->key_resvid ||
+                q.key == ctx->key_resvtype)
+                se.cflags[row] |= CF_OFFERING;
         }
-        if (row < C && !th.g.empty()) {
+        if (row < C && !se.th.g.empty()) {
             // keys the class's topology groups narrow (AddRequirements adds zone In [domain] even when the pod does
             // not constrain the zone): carried as Exists, skipped by Compatible, merged as the base requirement
-            for (int k : th.neutral[row]) {
+            for (int k : se.th.neutral[row]) {
                 ReqHdr h{};
                 h.flags = RF_DEF | RF_CMP;
-                chdr[(size_t)row * K + k] = h;
+                se.chdr[(size_t)row * K + k] = h;
                 nk++;
-                ckeys.push_back(k);
-                ckneu.push_back(1);
-                cwsoff.push_back(so);
-                so += nw[k];
-                if (k == c->key_zone || k == c->key_ct || k == c->key_zoneid || k == c->key_resvid || k == c->key_resvtype)
-                    cflags[row] |= CF_OFFERING;
+                se.ckeys.push_back(k);
+                se.ckneu.push_back(1);
+                se.cwsoff.push_back(so);
+                so += se.nw[k];
+                if (k == ctx->key_zone || k == ctx->key_ct || k == ctx->key_zoneid || k == ctx->key_resvid || k == ctx->key_resvtype)
+                    se.cflags[row] |= CF_OFFERING;
             }
-            if (!th.cons[row].empty() || !th.rec[row].empty()) cflags[row] |= CF_TOPO;
-            if (!th.cons[row].empty()) cflags[row] |= CF_TOPO_CONS;
+            if (!se.th.cons[row].empty() || !se.th.rec[row].empty()) se.cflags[row] |= CF_TOPO;
+            if (!se.th.cons[row].empty()) se.cflags[row] |= CF_TOPO_CONS;
             bool qrec = true;
-            for (int gi : th.rec[row]) {
-                const HGroup& g = th.g[gi];
+            for (int gi : se.th.rec[row]) {
+                const HGroup& g = se.th.g[gi];
                 // an owner's pods satisfy their own node filter: the group's when the owner's semantics are the first
                 // owner's (an owner of the identity with another filter records through the group's, topo_record)
                 if (!g.inverse && g.type == KP_TOPO_SPREAD && (g.pol & 1) && !g.same[row]) qrec = false;
             }
-            if (qrec) cflags[row] |= CF_TOPO_QREC;
+            if (qrec) se.cflags[row] |= CF_TOPO_QREC;
         }
-        if (nk == 0) cflags[row] |= CF_NOKEYS;  // no requirement keys: NodeClaim.Add = tolerations + Fits (+ minValues)
+        if (nk == 0) se.cflags[row] |= CF_NOKEYS;  // no requirement keys: NodeClaim.Add = tolerations + Fits (+ minValues)
         if (nk > KP_MAX_CLASS_KEYS || so > KP_MAX_SCR_WORDS) return false;
-        koff[row + 1] = (int)ckeys.size();
-        if (row < C) xkoff[row + 1] = (int)xkeys.size();
+        se.koff[row + 1] = (int)se.ckeys.size();
+        if (row < C) se.xkoff[row + 1] = (int)se.xkeys.size();
         return true;
     };
     for (int i = 0; i < C; i++)
-        if (!encode(i, creq[i])) return fail(ctx, KP_E_UNSUPPORTED, "pod class constrains too many labels");
+        if (!encode(i, se.creq[i])) return fail(ctx, KP_E_UNSUPPORTED, "pod class constrains too many labels");
     for (int j = 0; j < NT; j++) {
-        if (!encode(C + j, treq[j])) return fail(ctx, KP_E_UNSUPPORTED, "NodePool constrains too many labels");
+        if (!encode(C + j, se.treq[j])) return fail(ctx, KP_E_UNSUPPORTED, "NodePool constrains too many labels");
         int q = 0;
-        for (auto& kv : treq[j])
+        for (auto& kv : se.treq[j])
             if (kv.second.has_min) {
-                min_keys[(size_t)j * KP_MAX_CLASS_KEYS + q++] = kv.first;
-                c->any_min_values = true;
-                c->max_min_values = std::max(c->max_min_values, (int)kv.second.minv);
-                if (kv.first < c->Kcat && (c->cat_kflags[kv.first] & KF_CAT_MULTI)) c->min_multi = true;
+                se.min_keys[(size_t)j * KP_MAX_CLASS_KEYS + q++] = kv.first;
+                ctx->any_min_values = true;
+                ctx->max_min_values = std::max(ctx->max_min_values, (int)kv.second.minv);
+                if (kv.first < ctx->Kcat && (ctx->cat_kflags[kv.first] & KF_CAT_MULTI)) ctx->min_multi = true;
             }
     }
     // spread node-filter rows after the templates: each Honor spread group's filter is its owner's rows
-    std::vector<int2> frow(C, make_int2(0, 0));
-    xkoff.resize(CT + 1, xkoff[C]);  // template rows: no keys
+    se.frow.assign(C, make_int2(0, 0));
+    se.xkoff.resize(CT + 1, se.xkoff[C]);  // template rows: no keys
     {
         int F = 0;
-        for (int i = 0; i < C; i++) F += (int)cfilt[i].size();
-        chdr.resize((size_t)(CT + F) * K);
-        cwords.resize((size_t)(CT + F) * DW, 0);
+        for (int i = 0; i < C; i++) F += (int)se.cfilt[i].size();
+        se.chdr.resize((size_t)(CT + F) * K);
+        se.cwords.resize((size_t)(CT + F) * DW, 0);
         int row = CT;
         for (int i = 0; i < C; i++) {
-            frow[i] = make_int2(row, (int)cfilt[i].size());
-            for (auto& rq : cfilt[i]) {
+            se.frow[i] = make_int2(row, (int)se.cfilt[i].size());
+            for (auto& rq : se.cfilt[i]) {
                 for (auto& kv : rq) {
                     const HReq& q = kv.second;
                     ReqHdr h{};
                     h.flags = RF_DEF | (q.complement ? RF_CMP : 0u) | (q.has_gt ? RF_GT : 0u) | (q.has_lt ? RF_LT : 0u);
                     h.gt = q.gt;
                     h.lt = q.lt;
-                    chdr[(size_t)row * K + q.key] = h;
-                    for (int vv : q.vals) cwords[(size_t)row * DW + woff[q.key] + vv / 64] |= 1ull << (vv % 64);
-                    xkeys.push_back(q.key);
+                    se.chdr[(size_t)row * K + q.key] = h;
+                    for (int vv : q.vals) se.cwords[(size_t)row * DW + se.woff[q.key] + vv / 64] |= 1ull << (vv % 64);
+                    se.xkeys.push_back(q.key);
                 }
-                xkoff.push_back((int)xkeys.size());
+                se.xkoff.push_back((int)se.xkeys.size());
                 row++;
             }
         }
     }
+    return KP_OK;
+}
+
+static kp_status solve_template_tables(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int T = ctx->T, TW = ctx->TW, R = ctx->R, C = in->n_classes, NT = se.NT;
     // ---- templates: taints, daemon overhead, limits, instance-type rows ----
-    std::vector<uint64_t> tol(std::max(C, 1), 0);
-    std::vector<int64_t> daemon((size_t)NT * R, 0), remaining((size_t)NT * R, 0);
-    std::vector<uint8_t> limit_set((size_t)NT * R, 0);
-    std::vector<uint64_t> rows((size_t)NT * TW, 0);
-    c->tmpl_np.assign(npo.begin(), npo.end());
+    se.tol.assign(std::max(C, 1), 0);
+    se.daemon.assign((size_t)NT * R, 0), se.remaining.assign((size_t)NT * R, 0);
+    se.limit_set.assign((size_t)NT * R, 0);
+    se.rows.assign((size_t)NT * TW, 0);
+    ctx->tmpl_np.assign(se.npo.begin(), se.npo.end());
     for (int j = 0; j < NT; j++) {
-        const kp_nodepool& np = in->nodepools[npo[j]];
+        const kp_nodepool& np = in->nodepools[se.npo[j]];
         for (int i = 0; i < C; i++) {
             bool all = true;
             for (int q = 0; q < np.n_taints && all; q++)
                 all = tolerates(np.taints[q], in->classes[i].tolerations, in->classes[i].n_tolerations);
-            if (all) tol[i] |= 1ull << j;
+            if (all) se.tol[i] |= 1ull << j;
         }
         for (int r = 0; r < R; r++) {
-            if (np.daemon_overhead) daemon[(size_t)j * R + r] = np.daemon_overhead[r];
+            if (np.daemon_overhead) se.daemon[(size_t)j * R + r] = np.daemon_overhead[r];
             if (np.limit_set && np.limit_set[r]) {
-                limit_set[(size_t)j * R + r] = 1;
-                remaining[(size_t)j * R + r] = np.limit_remaining[r];
+                se.limit_set[(size_t)j * R + r] = 1;
+                se.remaining[(size_t)j * R + r] = np.limit_remaining[r];
             }
         }
         if (np.n_types < 0) {
-            for (int t = 0; t < T; t++) rows[(size_t)j * TW + t / 64] |= 1ull << (t % 64);
+            for (int t = 0; t < T; t++) se.rows[(size_t)j * TW + t / 64] |= 1ull << (t % 64);
         } else {
             for (int q = 0; q < np.n_types; q++) {
                 const int t = np.type_index[q];
                 if (t < 0 || t >= T) return fail(ctx, KP_E_INVALID, "nodepool type_index out of range");
-                rows[(size_t)j * TW + t / 64] |= 1ull << (t % 64);
+                se.rows[(size_t)j * TW + t / 64] |= 1ull << (t % 64);
             }
         }
     }
     for (int i = 0; i < C; i++)
-        if (hblock[i]) tol[i] = 0;  // hostname requirement no new or in-flight NodeClaim can satisfy
+        if (se.hblock[i]) se.tol[i] = 0;  // hostname requirement no new or in-flight NodeClaim can satisfy
+    return KP_OK;
+}
+
+static kp_status solve_existing_digests(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int R = ctx->R, C = in->n_classes, E = se.E, K = se.K, DW = se.DW;
     // ---- existing nodes: digests, tolerations ----
-    const int EW = (E + 63) / 64;
-    std::vector<ReqHdr> exhdr((size_t)std::max(E, 1) * K);
-    memset(exhdr.data(), 0, exhdr.size() * sizeof(ReqHdr));
-    std::vector<uint64_t> exw((size_t)std::max(E, 1) * DW, 0), extol((size_t)std::max(C, 1) * std::max(EW, 1), 0);
-    std::vector<int64_t> exav((size_t)std::max(E, 1) * R, 0), exrq((size_t)std::max(E, 1) * R, 0);
+    const int EW = se.EW = (E + 63) / 64;
+    se.exhdr.resize((size_t)std::max(E, 1) * K);
+    memset(se.exhdr.data(), 0, se.exhdr.size() * sizeof(ReqHdr));
+    se.exw.assign((size_t)std::max(E, 1) * DW, 0), se.extol.assign((size_t)std::max(C, 1) * std::max(EW, 1), 0);
+    se.exav.assign((size_t)std::max(E, 1) * R, 0), se.exrq.assign((size_t)std::max(E, 1) * R, 0);
     for (int j = 0; j < E; j++) {
         const kp_existing_node& en = in->existing[j];
-        for (auto& kv : exlab[j]) {
-            ReqHdr& h = exhdr[(size_t)j * K + kv.first];
+        for (auto& kv : se.exlab[j]) {
+            ReqHdr& h = se.exhdr[(size_t)j * K + kv.first];
             h.flags = RF_DEF;
-            exw[(size_t)j * DW + woff[kv.first] + kv.second / 64] |= 1ull << (kv.second % 64);
+            se.exw[(size_t)j * DW + se.woff[kv.first] + kv.second / 64] |= 1ull << (kv.second % 64);
         }
         for (int r = 0; r < R; r++) {
-            exav[(size_t)j * R + r] = en.available[r];
-            exrq[(size_t)j * R + r] = en.requests ? en.requests[r] : 0;
+            se.exav[(size_t)j * R + r] = en.available[r];
+            se.exrq[(size_t)j * R + r] = en.requests ? en.requests[r] : 0;
         }
         for (int i = 0; i < C; i++) {
             bool all = true;
             for (int q = 0; q < en.n_taints && all; q++)
                 all = tolerates(en.taints[q], in->classes[i].tolerations, in->classes[i].n_tolerations);
-            if (all) extol[(size_t)i * EW + j / 64] |= 1ull << (j % 64);
+            if (all) se.extol[(size_t)i * EW + j / 64] |= 1ull << (j % 64);
         }
     }
-    PREP_MARK(2);
+    return KP_OK;
+}
+
+static kp_status solve_pods(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int R = ctx->R, P = in->pods.n_pods, C = in->n_classes, NT = se.NT;
     // ---- pods ----
     // per-pod arrays: pinned ctx buffers kept across calls (no allocation or page faults per solve, DMA uploads); the
     // previous solve's uploads from them have finished before they are rewritten
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(c->p_pcls.ensure(std::max(P, 1)));
-    HIPCHK(c->p_pshape.ensure(std::max(P, 1)));
-    HIPCHK(c->p_preq.ensure((size_t)std::max(P, 1) * R));
-    HIPCHK(c->p_fields.ensure((size_t)std::max(P, 1) * 4));
-    int32_t* const pcls = c->p_pcls.p;
-    int32_t* const pshape = c->p_pshape.p;
-    int64_t* const preq = c->p_preq.p;
-    int64_t* const fields = c->p_fields.p;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx->p_pcls.ensure(std::max(P, 1)));
+    HIPCHK(ctx->p_pshape.ensure(std::max(P, 1)));
+    HIPCHK(ctx->p_preq.ensure((size_t)std::max(P, 1) * R));
+    HIPCHK(ctx->p_fields.ensure((size_t)std::max(P, 1) * 4));
+    int32_t* const pcls = ctx->p_pcls.p;
+    int32_t* const pshape = ctx->p_pshape.p;
+    int64_t* const preq = ctx->p_preq.p;
+    int64_t* const fields = ctx->p_fields.p;
     int cpu_axis = -1, mem_axis = -1;
     for (int r = 0; r < R; r++) {
-        if (c->resource_names[r] == "cpu") cpu_axis = r;
-        if (c->resource_names[r] == "memory") mem_axis = r;
+        if (ctx->resource_names[r] == "cpu") cpu_axis = r;
+        if (ctx->resource_names[r] == "memory") mem_axis = r;
     }
     if (cpu_axis < 0 || mem_axis < 0) return fail(ctx, KP_E_INVALID, "catalog lacks cpu/memory axes");
     std::vector<uint8_t> active(R, 0);
     for (int j = 0; j < NT; j++)
         for (int r = 0; r < R; r++)
-            if (daemon[(size_t)j * R + r] != 0) active[r] = 1;
+            if (se.daemon[(size_t)j * R + r] != 0) active[r] = 1;
     // shapes: (class, requests) interned in an open-addressing table of shape ids; a shape's requests point at the
     // pinned row of its first pod (relaxation stages share the row of the shape they relax)
     struct ShapeRec {
@@ -2344,7 +2410,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
         const int64_t* req;
     };
     std::vector<ShapeRec> shapes;
-    std::vector<int32_t>& stab = c->h_shape_tab;
+    std::vector<int32_t>& stab = ctx->h_shape_tab;
     size_t SHT = 1024;
     while (SHT < (size_t)P * 2) SHT <<= 1;
     if (stab.size() < SHT) stab.resize(SHT);
@@ -2378,8 +2444,8 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     // open-addressing table over those prefixes (ctx scratch, cleared per call)
     size_t HT = 1024;
     while (HT < (size_t)P * 2) HT <<= 1;
-    std::vector<uint64_t>& uid_k = c->h_uid_k;
-    std::vector<int32_t>& uid_p = c->h_uid_p;
+    std::vector<uint64_t>& uid_k = ctx->h_uid_k;
+    std::vector<int32_t>& uid_p = ctx->h_uid_p;
     if (uid_k.size() < HT) {
         uid_k.resize(HT);
         uid_p.resize(HT);
@@ -2456,8 +2522,8 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     // KPSIM_PREP_SPLIT_MIN: the batch size from which the two passes run side by side (tests force small batches)
     static const int split_min = getenv("KPSIM_PREP_SPLIT_MIN") ? atoi(getenv("KPSIM_PREP_SPLIT_MIN")) : 16384;
     if (P >= split_min) {
-        c->pool.grow(2);
-        if (!c->pool.run(2, [&](int t) { t == 0 ? pod_rows() : pod_keys(); }))
+        ctx->pool.grow(2);
+        if (!ctx->pool.run(2, [&](int t) { t == 0 ? pod_rows() : pod_keys(); }))
             return fail(ctx, KP_E_INVALID, "kp_solve_prepare: host error in a worker thread");
     } else {
         pod_rows();
@@ -2476,85 +2542,95 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     }
     PREP_MARK(3);
     // relaxation stages of every shape: shape_next[s] = the shape of (relax_next[class of s], the same requests)
-    std::vector<int32_t> shape_next;
-    if (!c->pref.relax_next.empty()) {
+    if (!ctx->pref.relax_next.empty()) {
         for (size_t sid = 0; sid < shapes.size(); sid++) {
-            const int nx = c->pref.relax_next[shapes[sid].cls];
-            shape_next.push_back(nx >= 0 ? shape_id(nx, shapes[sid].req) : -1);
+            const int nx = ctx->pref.relax_next[shapes[sid].cls];
+            se.shape_next.push_back(nx >= 0 ? shape_id(nx, shapes[sid].req) : -1);
         }
     }
-    KpDev& d = c->dev;
+    KpDev& d = ctx->dev;
     d = KpDev{};
     d.n_active = 0;
     for (int r = 0; r < R; r++)
         if (active[r]) d.active_axes[d.n_active++] = r;
-    PREP_MARK(4);
+    return KP_OK;
+}
+
+static kp_status solve_upload(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    kp_ctx* c = ctx;
+    const int TW = c->TW, R = c->R, P = in->pods.n_pods, E = se.E, NT = se.NT, CT = se.CT, K = se.K, DW = se.DW;
     // ---- device buffers ----
     hipStream_t s = c->stream;
     std::vector<ReqHdr> empty_hdr(K);
     memset(empty_hdr.data(), 0, empty_hdr.size() * sizeof(ReqHdr));
     std::vector<uint64_t> empty_words(DW, 0);
-    HIPCHK(c->d_kflags.upload(kflags, s));
-    HIPCHK(c->d_kcat.upload(kcat, s));
-    HIPCHK(c->d_kmulti.upload(kmulti, s));
-    HIPCHK(c->d_woff.upload(woff, s));
-    HIPCHK(c->d_nw.upload(nw, s));
-    HIPCHK(c->d_nval.upload(nval, s));
-    HIPCHK(c->d_vbase.upload(vbase, s));
-    if (isint.empty()) {
-        isint.push_back(0);
-        ival.push_back(0);
+    HIPCHK(c->d_kflags.upload(se.kflags, s));
+    HIPCHK(c->d_kcat.upload(se.kcat, s));
+    HIPCHK(c->d_kmulti.upload(se.kmulti, s));
+    HIPCHK(c->d_woff.upload(se.woff, s));
+    HIPCHK(c->d_nw.upload(se.nw, s));
+    HIPCHK(c->d_nval.upload(se.nval, s));
+    HIPCHK(c->d_vbase.upload(se.vbase, s));
+    if (se.isint.empty()) {
+        se.isint.push_back(0);
+        se.ival.push_back(0);
     }
-    HIPCHK(c->d_val_isint.upload(isint, s));
-    HIPCHK(c->d_val_int.upload(ival, s));
-    HIPCHK(c->d_cls_koff.upload(koff, s));
-    if (ckeys.empty()) {
-        ckeys.push_back(0);
-        cwsoff.push_back(0);
-        ckneu.push_back(0);
+    HIPCHK(c->d_val_isint.upload(se.isint, s));
+    HIPCHK(c->d_val_int.upload(se.ival, s));
+    HIPCHK(c->d_cls_koff.upload(se.koff, s));
+    if (se.ckeys.empty()) {
+        se.ckeys.push_back(0);
+        se.cwsoff.push_back(0);
+        se.ckneu.push_back(0);
     }
-    HIPCHK(c->d_cls_kneutral.upload(ckneu, s));
-    HIPCHK(c->d_cls_keys.upload(ckeys, s));
-    HIPCHK(c->d_cls_wsoff.upload(cwsoff, s));
-    HIPCHK(c->d_cls_hdr.upload(chdr, s));
-    HIPCHK(c->d_cls_words.upload(cwords, s));
-    HIPCHK(c->d_cls_flags.upload(cflags, s));
+    HIPCHK(c->d_cls_kneutral.upload(se.ckneu, s));
+    HIPCHK(c->d_cls_keys.upload(se.ckeys, s));
+    HIPCHK(c->d_cls_wsoff.upload(se.cwsoff, s));
+    HIPCHK(c->d_cls_hdr.upload(se.chdr, s));
+    HIPCHK(c->d_cls_words.upload(se.cwords, s));
+    HIPCHK(c->d_cls_flags.upload(se.cflags, s));
     HIPCHK(c->d_V.ensure((size_t)CT * TW));
-    HIPCHK(c->d_tmpl_rows.upload(rows, s));
+    HIPCHK(c->d_tmpl_rows.upload(se.rows, s));
     HIPCHK(c->d_tmpl_opts.ensure((size_t)std::max(NT, 1) * TW));
     HIPCHK(c->d_tmpl_ok.ensure(std::max(NT, 1)));
-    HIPCHK(c->d_tol.upload(tol, s));
-    HIPCHK(c->d_daemon.upload(daemon, s));
-    HIPCHK(c->d_limit_set.upload(limit_set, s));
-    HIPCHK(c->d_remaining.upload(remaining, s));
-    c->h_remaining = remaining;
-    HIPCHK(c->d_min_keys.upload(min_keys, s));
-    if (xkeys.empty()) xkeys.push_back(0);
-    HIPCHK(c->d_cls_xkoff.upload(xkoff, s));
-    HIPCHK(c->d_cls_xkeys.upload(xkeys, s));
-    HIPCHK(c->d_ex_hdr0.upload(exhdr, s));
-    HIPCHK(c->d_ex_words0.upload(exw, s));
-    HIPCHK(c->d_ex_hdr.ensure(exhdr.size()));
-    HIPCHK(c->d_ex_words.ensure(exw.size()));
-    HIPCHK(c->d_ex_avail.upload(exav, s));
-    HIPCHK(c->d_ex_req.upload(exrq, s));
+    HIPCHK(c->d_tol.upload(se.tol, s));
+    HIPCHK(c->d_daemon.upload(se.daemon, s));
+    HIPCHK(c->d_limit_set.upload(se.limit_set, s));
+    HIPCHK(c->d_remaining.upload(se.remaining, s));
+    c->h_remaining = se.remaining;
+    HIPCHK(c->d_min_keys.upload(se.min_keys, s));
+    if (se.xkeys.empty()) se.xkeys.push_back(0);
+    HIPCHK(c->d_cls_xkoff.upload(se.xkoff, s));
+    HIPCHK(c->d_cls_xkeys.upload(se.xkeys, s));
+    HIPCHK(c->d_ex_hdr0.upload(se.exhdr, s));
+    HIPCHK(c->d_ex_words0.upload(se.exw, s));
+    HIPCHK(c->d_ex_hdr.ensure(se.exhdr.size()));
+    HIPCHK(c->d_ex_words.ensure(se.exw.size()));
+    HIPCHK(c->d_ex_avail.upload(se.exav, s));
+    HIPCHK(c->d_ex_req.upload(se.exrq, s));
     HIPCHK(c->d_ex_head.ensure((size_t)KP_MAX_R * std::max(E, 1)));
     HIPCHK(c->d_ex_static.ensure(std::max(E, 1)));
-    HIPCHK(c->d_ex_tol.upload(extol, s));
-    HIPCHK(c->d_XT.ensure(extol.size()));
-    HIPCHK(c->d_pod_cls.upload(pcls, P, s));
-    HIPCHK(c->d_pod_shape.upload(pshape, P, s));
-    if (!shape_next.empty()) {
-        HIPCHK(c->d_pod_cls0.upload(pcls, P, s));
-        HIPCHK(c->d_pod_shape0.upload(pshape, P, s));
+    HIPCHK(c->d_ex_tol.upload(se.extol, s));
+    HIPCHK(c->d_XT.ensure(se.extol.size()));
+    HIPCHK(c->d_pod_cls.upload(c->p_pcls.p, P, s));
+    HIPCHK(c->d_pod_shape.upload(c->p_pshape.p, P, s));
+    if (!se.shape_next.empty()) {
+        HIPCHK(c->d_pod_cls0.upload(c->p_pcls.p, P, s));
+        HIPCHK(c->d_pod_shape0.upload(c->p_pshape.p, P, s));
         HIPCHK(c->d_relax_next.upload(c->pref.relax_next, s));
-        HIPCHK(c->d_shape_next.upload(shape_next, s));
+        HIPCHK(c->d_shape_next.upload(se.shape_next, s));
         HIPCHK(c->d_last_ep.ensure(std::max(P, 1)));
     }
-    HIPCHK(c->d_pod_req.upload(preq, (size_t)P * R, s));
-    HIPCHK(c->d_sort_fields.upload(fields, (size_t)P * 4, s));
+    HIPCHK(c->d_pod_req.upload(c->p_preq.p, (size_t)P * R, s));
+    HIPCHK(c->d_sort_fields.upload(c->p_fields.p, (size_t)P * 4, s));
     HIPCHK(c->d_empty_hdr.upload(empty_hdr, s));
     HIPCHK(c->d_empty_words.upload(empty_words, s));
+    return KP_OK;
+}
+
+static kp_status solve_plan_nodeclaims(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    kp_ctx* c = ctx;
+    const int T = c->T, TW = c->TW, R = c->R, P = in->pods.n_pods, C = in->n_classes, E = se.E, K = se.K, DW = se.DW;
     // in-flight NodeClaim capacity.  A self-selecting hostname anti-affinity (required, or preferred under Respect: each
     // pod takes a new NodeClaim before anything is relaxed) puts every pod of its class on a host of its own, a
     // self-selecting hostname spread at most maxSkew per host: when that lower bound exceeds the first plan
@@ -2564,7 +2640,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     {
         std::vector<int64_t> ccount(std::max(C, 1), 0);
         for (int p = 0; p < P; p++) ccount[in->pods.class_id[p]]++;
-        for (const HGroup& g : th.g)
+        for (const HGroup& g : se.th.g)
             if (!g.inverse && g.host) {
                 int64_t m = 0;  // pods of the self-selecting classes that own the group
                 for (int o = 0; o < C; o++)
@@ -2578,7 +2654,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     int64_t plan = c->nc_cap_once > 0 ? c->nc_cap_once : KP_NC_FIRST;
     c->nc_cap_once = 0;
     if (dense + dense / 8 + 64 > plan) plan = dense + dense / 8 + 64;
-    const int NCcap = (int)std::min<int64_t>(std::min<int64_t>(plan, KP_MAX_NC), std::max(P, 1));
+    const int NCcap = se.NCcap = (int)std::min<int64_t>(std::min<int64_t>(plan, KP_MAX_NC), std::max(P, 1));
     c->last_plan_nc = NCcap;
     HIPCHK(c->d_nc_hdr.ensure((size_t)NCcap * K));
     HIPCHK(c->d_nc_words.ensure((size_t)NCcap * DW));
@@ -2602,16 +2678,138 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     HIPCHK(c->d_nc_nopts.ensure(NCcap));
     HIPCHK(c->d_nc_valid.ensure(NCcap));
     HIPCHK(c->d_nc_ntypes.ensure(NCcap));
-    const int M = in->max_instance_types > 0 ? std::min(in->max_instance_types, T) : T;
+    const int M = se.M = in->max_instance_types > 0 ? std::min(in->max_instance_types, T) : T;
     HIPCHK(c->d_nc_types.ensure((size_t)NCcap * M));
     HIPCHK(c->d_stats.ensure(ST_COUNT));
+    return KP_OK;
+}
+
+static bool hreq_has(const kp_ctx* c, const HReq& q, int v) {  // Requirement.Has by value id
+    const bool in = std::binary_search(q.vals.begin(), q.vals.end(), v);
+    if (!q.complement) return in;
+    if (in) return false;
+    if (!q.has_gt && !q.has_lt) return true;
+    int64_t x = 0;
+    if (!go_atoi(c->sol.keys[q.key].vals[v].c_str(), x)) return false;
+    return !((q.has_gt && q.gt >= x) || (q.has_lt && q.lt <= x));
+}
+
+// countDomains over the pods bound to existing nodes (forward groups that select the pod's class; a spread
+// group's node filter against the node's labels and taints) and updateInverseAffinities (the inverse
+// anti-affinity groups of the bound pod's class record the node's domain) — [core] scheduling/topology.go,
+// restated in oracle/orc_solve.cpp build_topology.  A node without the key's label is not counted.
+static kp_status topo_count_bound(kp_ctx* ctx, const kp_solve_input* in, const SolveEnc& se, int HN, std::vector<int32_t>& hc0,
+                                  std::vector<int32_t>& tpos0, std::vector<int32_t>& tcnt0, std::vector<uint64_t>& tknown0,
+                                  std::vector<int2>& tce_hosts, const std::vector<int>& tce_hosts_g) {
+    kp_ctx* c = ctx;
+    const int C = in->n_classes, E = se.E, G = (int)se.th.g.size();
+    auto node_val = [&](int j, int k) {
+        for (auto& e : se.exlab[j])
+            if (e.first == k) return e.second;
+        return -1;
+    };
+    // TopologyNodeFilter.MatchesRequirements: Compatible(node labels, a filter row of the owner), no wk allowance
+    auto node_compatible_with = [&](int j, int owner) {
+        for (auto& rq : se.cfilt[owner]) {
+            bool ok = true;
+            for (auto& kv : rq) {
+                const HReq& q = kv.second;
+                const int v = node_val(j, kv.first);
+                const bool qno = (q.complement && !q.vals.empty()) || (!q.complement && q.vals.empty());
+                if (v < 0) {
+                    if (!qno) ok = false;
+                } else if (!hreq_has(c, q, v)) {
+                    ok = false;
+                }
+                if (!ok) break;
+            }
+            if (ok) return true;
+        }
+        return false;
+    };
+    auto node_tolerated_by = [&](int j, int owner) {
+        const kp_existing_node& en = in->existing[j];
+        for (int q = 0; q < en.n_taints; q++)
+            if (!tolerates(en.taints[q], in->classes[owner].tolerations, in->classes[owner].n_tolerations)) return false;
+        return true;
+    };
+    c->h_tknown_dg.assign(tknown0.begin(), tknown0.end());  // buildDomainGroups only (consolidation probes)
+    // one bound pod of class b on node j; cand >= 0: a consolidation candidate's reschedulable pod, whose
+    // value-keyed contributions are also kept per candidate (a probe takes off the pods it reschedules)
+    auto count_pod = [&](int j, int b, int cand) -> bool {
+        for (int gi = 0; gi < G; gi++) {
+            const HGroup& g = se.th.g[gi];
+            if (g.inverse ? !g.memb[b] : !g.sel[b]) continue;
+            if (!g.inverse && g.type == KP_TOPO_SPREAD) {
+                if ((g.pol & 1) && !node_compatible_with(j, g.owner)) continue;
+                if ((g.pol & 2) && !node_tolerated_by(j, g.owner)) continue;
+            }
+            if (g.host) {
+                if (hc0[(size_t)g.hrow * HN + j]++ == 0) tpos0[gi]++;
+                if (cand >= 0 && c->tg_host_aff[gi]) c->cons_hdec[cand][gi]++;
+            } else {
+                const int v = node_val(j, g.key);
+                if (v < 0) continue;
+                if (v >= 64) return false;
+                tcnt0[(size_t)gi * 64 + v]++;
+                tknown0[gi] |= 1ull << v;
+                if (cand >= 0) {
+                    auto& row = c->cons_dec[cand][gi];
+                    if (row.empty()) row.assign(64, 0);
+                    row[v]++;
+                }
+            }
+        }
+        return true;
+    };
+    for (int i = 0; i < in->n_bound; i++) {
+        const int j = in->bound_node[i], b = in->bound_class[i];
+        if (j < 0 || j >= E || b < 0 || b >= C) return fail(ctx, KP_E_INVALID, "bound pod index out of range");
+        if (!count_pod(j, b, -1)) return fail(ctx, KP_E_UNSUPPORTED, "topology key with more than 64 values");
+    }
+    // kp_consolidate_prepare: each candidate's reschedulable pods are bound to its node in the cluster
+    c->cons_dec.assign(c->cons_extra_ncand, {});
+    c->cons_hdec.assign(c->cons_extra_ncand, {});
+    c->cons_hlost.assign(c->cons_extra_ncand, {});
+    std::vector<int> cand_node(c->cons_extra_ncand, -1);
+    for (auto& e : c->cons_extra) {
+        if (!count_pod(e[0], in->pods.class_id[e[1]], e[2]))
+            return fail(ctx, KP_E_UNSUPPORTED, "topology key with more than 64 values");
+        cand_node[e[2]] = e[0];
+    }
+    for (int ci = 0; ci < c->cons_extra_ncand; ci++)
+        for (auto& kv : c->cons_hdec[ci])
+            if (hc0[(size_t)se.th.g[kv.first].hrow * HN + cand_node[ci]] == kv.second) c->cons_hlost[ci].push_back(kv.first);
+    // hostname lists (KpTopoCons.hdom): a candidate's node keeps a selected pod its probe does not reschedule
+    std::map<int, int> node_cand;
+    for (int ci = 0; ci < c->cons_extra_ncand; ci++) node_cand[cand_node[ci]] = ci;
+    for (size_t q = 0; q < tce_hosts.size(); q++) {
+        const int j = tce_hosts[q].x, gi = tce_hosts_g[q];
+        int left = hc0[(size_t)se.th.g[gi].hrow * HN + j];
+        const auto nc = node_cand.find(j);
+        if (nc != node_cand.end()) {
+            const auto dec = c->cons_hdec[nc->second].find(gi);
+            if (dec != c->cons_hdec[nc->second].end()) left -= dec->second;
+        }
+        tce_hosts[q].y = left > 0;
+    }
+    c->h_tpos0.assign(tpos0.begin(), tpos0.end());
+    return KP_OK;
+}
+
+static kp_status solve_topology_tables(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    kp_ctx* c = ctx;
+    const int T = c->T, TW = c->TW, P = in->pods.n_pods, C = in->n_classes;
+    const int E = se.E, NT = se.NT, K = se.K, DW = se.DW, NCcap = se.NCcap;
+    hipStream_t s = c->stream;
+    KpDev& d = c->dev;
     // ---- topology: groups, initial domains (buildDomainGroups), per-class group lists, tie-break ranks ----
-    const int G = (int)th.g.size();
+    const int G = (int)se.th.g.size();
     c->tg_G = G;
-    c->tg_HG = th.n_host;
+    c->tg_HG = se.th.n_host;
     c->tg_host_aff.assign(std::max(G, 1), 0);
     for (int gi = 0; gi < G; gi++)
-        c->tg_host_aff[gi] = th.g[gi].host && th.g[gi].type == KP_TOPO_AFFINITY && !th.g[gi].inverse;
+        c->tg_host_aff[gi] = se.th.g[gi].host && se.th.g[gi].type == KP_TOPO_AFFINITY && !se.th.g[gi].inverse;
     c->cons_dec.assign(c->cons_extra_ncand, {});
     c->cons_hdec.assign(c->cons_extra_ncand, {});
     c->cons_hlost.assign(c->cons_extra_ncand, {});
@@ -2632,17 +2830,8 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
         // hostname rows: existing nodes, then NodeClaim ids 0 .. NCcap, the last a spare that stays 0 (a template
         // evaluation for a NodeClaim at capacity reads it; the capacity check then reports the overflow)
         const int HN = E + NCcap + 1;
-        std::vector<int32_t> hc0((size_t)std::max(1, th.n_host) * HN, 0);
+        std::vector<int32_t> hc0((size_t)std::max(1, se.th.n_host) * HN, 0);
         if (G > 0) {
-            auto hreq_has = [&](const HReq& q, int v) {
-                const bool in = std::binary_search(q.vals.begin(), q.vals.end(), v);
-                if (!q.complement) return in;
-                if (in) return false;
-                if (!q.has_gt && !q.has_lt) return true;
-                int64_t x = 0;
-                if (!go_atoi(c->sol.keys[q.key].vals[v].c_str(), x)) return false;
-                return !((q.has_gt && q.gt >= x) || (q.has_lt && q.lt <= x));
-            };
             // buildDomainGroups: value → the NodePools (templates) offering it, over every NodePool × its types
             std::map<int, std::map<int, std::vector<int>>> dg;
             auto domains_of = [&](int k) -> const std::map<int, std::vector<int>>& {
@@ -2651,10 +2840,10 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
                 std::map<int, std::vector<int>>& m = dg[k];
                 const int mi = k < c->Kcat ? c->cat_multi[k] : -1;
                 for (int j = 0; j < NT; j++) {
-                    auto npit = treq[j].find(k);
-                    const bool hp = npit != treq[j].end();
+                    auto npit = se.treq[j].find(k);
+                    const bool hp = npit != se.treq[j].end();
                     for (int t = 0; t < T; t++) {
-                        if (!((rows[(size_t)j * TW + t / 64] >> (t % 64)) & 1ull)) continue;
+                        if (!((se.rows[(size_t)j * TW + t / 64] >> (t % 64)) & 1ull)) continue;
                         const int st = mi >= 0 ? c->h_multi_state[(size_t)mi * T + t] : KP_LABEL_ABSENT;
                         const bool ht = st != KP_LABEL_ABSENT;
                         if (!hp && !ht) continue;
@@ -2662,7 +2851,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
                         if (hp && ht) {
                             for (uint64_t x = tm; x; x &= x - 1) {
                                 const int v = __builtin_ctzll(x);
-                                if (hreq_has(npit->second, v)) m[v].push_back(j);
+                                if (hreq_has(c, npit->second, v)) m[v].push_back(j);
                             }
                         } else if (hp) {
                             for (int v : npit->second.vals) m[v].push_back(j);  // requirement.Values()
@@ -2676,19 +2865,19 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
                 return m;
             };
             auto owner_tolerates = [&](int owner, int j) {
-                const kp_nodepool& np = in->nodepools[npo[j]];
+                const kp_nodepool& np = in->nodepools[se.npo[j]];
                 for (int q = 0; q < np.n_taints; q++)
                     if (!tolerates(np.taints[q], in->classes[owner].tolerations, in->classes[owner].n_tolerations)) return false;
                 return true;
             };
             for (int gi = 0; gi < G; gi++) {
-                const HGroup& g = th.g[gi];
+                const HGroup& g = se.th.g[gi];
                 tinfo[gi] = make_int4(g.type | (g.inverse ? TG_INVERSE : 0) | (g.host ? TG_HOST : 0), g.key, g.skew, g.mindom);
                 thr_row[gi] = g.hrow;
                 towner[gi] = g.owner;
                 tpol[gi] = g.pol;
-                if (!g.inverse && g.type == KP_TOPO_SPREAD && (g.pol & 1)) tfrow[gi] = frow[g.owner];
-                tlate[gi] = th.g_late[gi];
+                if (!g.inverse && g.type == KP_TOPO_SPREAD && (g.pol & 1)) tfrow[gi] = se.frow[g.owner];
+                tlate[gi] = se.th.g_late[gi];
                 if (g.host) continue;
                 for (auto& kv : domains_of(g.key)) {
                     bool ok = !(g.type == KP_TOPO_SPREAD && (g.pol & 2));
@@ -2703,27 +2892,27 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
                 for (size_t r = 0; r < idx.size(); r++) vrank[(size_t)g.key * 64 + idx[r]] = (uint8_t)r;
             }
             for (int i = 0; i < C; i++) {
-                for (int e : th.cons[i]) tcl.push_back(e);
-                for (int e : th.rec[i]) trl.push_back(e);
+                for (int e : se.th.cons[i]) tcl.push_back(e);
+                for (int e : se.th.rec[i]) trl.push_back(e);
                 tcoff[i + 1] = (int)tcl.size();
                 troff[i + 1] = (int)trl.size();
             }
             // the entries' static operands (KpTopoCons / KpTopoRec): req_has over the encoded class digest, as the device
             // evaluates it
             auto digest_has = [&](int row, int k, int v) {
-                const ReqHdr& h = chdr[(size_t)row * K + k];
-                const bool bit = (cwords[(size_t)row * DW + woff[k] + v / 64] >> (v % 64)) & 1ull;
+                const ReqHdr& h = se.chdr[(size_t)row * K + k];
+                const bool bit = (se.cwords[(size_t)row * DW + se.woff[k] + v / 64] >> (v % 64)) & 1ull;
                 bool within = true;
                 if (h.flags & (RF_GT | RF_LT)) {
-                    const int b = vbase[k] + v;
-                    within = isint[b] && !((h.flags & RF_GT) && h.gt >= ival[b]) && !((h.flags & RF_LT) && h.lt <= ival[b]);
+                    const int b = se.vbase[k] + v;
+                    within = se.isint[b] && !((h.flags & RF_GT) && h.gt >= se.ival[b]) && !((h.flags & RF_LT) && h.lt <= se.ival[b]);
                 }
                 return (h.flags & RF_CMP) ? (!bit && within) : (bit && within);
             };
             for (int i = 0; i < C; i++) {
-                for (int e : th.cons[i]) {
+                for (int e : se.th.cons[i]) {
                     const int gi = e & 0x3FFFFFFF, self = (e >> 30) & 1;
-                    const HGroup& g = th.g[gi];
+                    const HGroup& g = se.th.g[gi];
                     KpTopoCons t{};
                     t.g = gi;
                     t.flags = g.type | (self << 2) | (g.host ? 8 : 0);
@@ -2733,7 +2922,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
                         t.key = -1 - g.hrow;
                         // nextDomainAffinity counts the positive domains podDomains admits: a pod requiring the hostname
                         // (In / NotIn a list; Exists admits every host) lists the existing nodes its values name
-                        const auto& rq = c->pref.has_strict[i] ? cstrict[i] : creq[i];
+                        const auto& rq = c->pref.has_strict[i] ? se.cstrict[i] : se.creq[i];
                         const auto hit = rq.find(g.key);
                         if (g.type == KP_TOPO_AFFINITY && self && !g.inverse && hit != rq.end()) {
                             const HReq& q = hit->second;
@@ -2741,8 +2930,8 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
                                 const int off = (int)tce_hosts.size();
                                 if (!q.has_gt && !q.has_lt)  // bounds admit no host name (Has parses an integer)
                                     for (int v : q.vals) {
-                                        const auto f = host_node.find(v);
-                                        if (f == host_node.end()) continue;
+                                        const auto f = se.host_node.find(v);
+                                        if (f == se.host_node.end()) continue;
                                         tce_hosts.push_back(make_int2(f->second, 0));
                                         tce_hosts_g.push_back(gi);
                                     }
@@ -2754,123 +2943,30 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
                         t.key = g.key;
                         // podDomains: the strict requirements' (no preferred term) requirement for the key, else Exists
                         const bool strict = c->pref.has_strict[i] != 0;
-                        const auto sit = strict ? cstrict[i].find(g.key) : cstrict[i].end();
-                        for (int v = 0; v < 64 && v < nval[g.key]; v++) {
+                        const auto sit = strict ? se.cstrict[i].find(g.key) : se.cstrict[i].end();
+                        for (int v = 0; v < 64 && v < se.nval[g.key]; v++) {
                             t.vmask |= 1ull << v;
-                            const bool has = strict ? (sit == cstrict[i].end() || hreq_has(sit->second, v)) : digest_has(i, g.key, v);
+                            const bool has = strict ? (sit == se.cstrict[i].end() || hreq_has(c, sit->second, v)) : digest_has(i, g.key, v);
                             if (has) t.podhas |= 1ull << v;
                         }
                     }
                     tce.push_back(t);
                 }
-                for (int gi : th.rec[i]) {
-                    const HGroup& g = th.g[gi];
+                for (int gi : se.th.rec[i]) {
+                    const HGroup& g = se.th.g[gi];
                     KpTopoRec r{};
                     r.g = gi;
                     r.flags = g.type | (g.inverse ? 4 : 0) | (g.host ? 8 : 0);
                     r.key = g.host ? -1 - g.hrow : g.key;
-                    r.late = th.g_late[gi];
+                    r.late = se.th.g_late[gi];
                     if (!g.inverse && g.type == KP_TOPO_SPREAD && (g.pol & 2))
                         for (int j = 0; j < NT; j++)
-                            if (!((tol[g.owner] >> j) & 1ull)) r.skip |= 1ull << j;
+                            if (!((se.tol[g.owner] >> j) & 1ull)) r.skip |= 1ull << j;
                     tre.push_back(r);
                 }
             }
-            // countDomains over the pods bound to existing nodes (forward groups that select the pod's class; a spread
-            // group's node filter against the node's labels and taints) and updateInverseAffinities (the inverse
-            // anti-affinity groups of the bound pod's class record the node's domain) — [core] scheduling/topology.go,
-            // restated in oracle/orc_solve.cpp build_topology.  A node without the key's label is not counted.
-            auto node_val = [&](int j, int k) {
-                for (auto& e : exlab[j])
-                    if (e.first == k) return e.second;
-                return -1;
-            };
-            // TopologyNodeFilter.MatchesRequirements: Compatible(node labels, a filter row of the owner), no wk allowance
-            auto node_compatible_with = [&](int j, int owner) {
-                for (auto& rq : cfilt[owner]) {
-                    bool ok = true;
-                    for (auto& kv : rq) {
-                        const HReq& q = kv.second;
-                        const int v = node_val(j, kv.first);
-                        const bool qno = (q.complement && !q.vals.empty()) || (!q.complement && q.vals.empty());
-                        if (v < 0) {
-                            if (!qno) ok = false;
-                        } else if (!hreq_has(q, v)) {
-                            ok = false;
-                        }
-                        if (!ok) break;
-                    }
-                    if (ok) return true;
-                }
-                return false;
-            };
-            auto node_tolerated_by = [&](int j, int owner) {
-                const kp_existing_node& en = in->existing[j];
-                for (int q = 0; q < en.n_taints; q++)
-                    if (!tolerates(en.taints[q], in->classes[owner].tolerations, in->classes[owner].n_tolerations)) return false;
-                return true;
-            };
-            c->h_tknown_dg.assign(tknown0.begin(), tknown0.end());  // buildDomainGroups only (consolidation probes)
-            // one bound pod of class b on node j; cand >= 0: a consolidation candidate's reschedulable pod, whose
-            // value-keyed contributions are also kept per candidate (a probe takes off the pods it reschedules)
-            auto count_pod = [&](int j, int b, int cand) -> bool {
-                for (int gi = 0; gi < G; gi++) {
-                    const HGroup& g = th.g[gi];
-                    if (g.inverse ? !g.memb[b] : !g.sel[b]) continue;
-                    if (!g.inverse && g.type == KP_TOPO_SPREAD) {
-                        if ((g.pol & 1) && !node_compatible_with(j, g.owner)) continue;
-                        if ((g.pol & 2) && !node_tolerated_by(j, g.owner)) continue;
-                    }
-                    if (g.host) {
-                        if (hc0[(size_t)g.hrow * HN + j]++ == 0) tpos0[gi]++;
-                        if (cand >= 0 && c->tg_host_aff[gi]) c->cons_hdec[cand][gi]++;
-                    } else {
-                        const int v = node_val(j, g.key);
-                        if (v < 0) continue;
-                        if (v >= 64) return false;
-                        tcnt0[(size_t)gi * 64 + v]++;
-                        tknown0[gi] |= 1ull << v;
-                        if (cand >= 0) {
-                            auto& row = c->cons_dec[cand][gi];
-                            if (row.empty()) row.assign(64, 0);
-                            row[v]++;
-                        }
-                    }
-                }
-                return true;
-            };
-            for (int i = 0; i < in->n_bound; i++) {
-                const int j = in->bound_node[i], b = in->bound_class[i];
-                if (j < 0 || j >= E || b < 0 || b >= C) return fail(ctx, KP_E_INVALID, "bound pod index out of range");
-                if (!count_pod(j, b, -1)) return fail(ctx, KP_E_UNSUPPORTED, "topology key with more than 64 values");
-            }
-            // kp_consolidate_prepare: each candidate's reschedulable pods are bound to its node in the cluster
-            c->cons_dec.assign(c->cons_extra_ncand, {});
-            c->cons_hdec.assign(c->cons_extra_ncand, {});
-            c->cons_hlost.assign(c->cons_extra_ncand, {});
-            std::vector<int> cand_node(c->cons_extra_ncand, -1);
-            for (auto& e : c->cons_extra) {
-                if (!count_pod(e[0], in->pods.class_id[e[1]], e[2]))
-                    return fail(ctx, KP_E_UNSUPPORTED, "topology key with more than 64 values");
-                cand_node[e[2]] = e[0];
-            }
-            for (int ci = 0; ci < c->cons_extra_ncand; ci++)
-                for (auto& kv : c->cons_hdec[ci])
-                    if (hc0[(size_t)th.g[kv.first].hrow * HN + cand_node[ci]] == kv.second) c->cons_hlost[ci].push_back(kv.first);
-            // hostname lists (KpTopoCons.hdom): a candidate's node keeps a selected pod its probe does not reschedule
-            std::map<int, int> node_cand;
-            for (int ci = 0; ci < c->cons_extra_ncand; ci++) node_cand[cand_node[ci]] = ci;
-            for (size_t q = 0; q < tce_hosts.size(); q++) {
-                const int j = tce_hosts[q].x, gi = tce_hosts_g[q];
-                int left = hc0[(size_t)th.g[gi].hrow * HN + j];
-                const auto nc = node_cand.find(j);
-                if (nc != node_cand.end()) {
-                    const auto dec = c->cons_hdec[nc->second].find(gi);
-                    if (dec != c->cons_hdec[nc->second].end()) left -= dec->second;
-                }
-                tce_hosts[q].y = left > 0;
-            }
-            c->h_tpos0.assign(tpos0.begin(), tpos0.end());
+            const kp_status bs = topo_count_bound(ctx, in, se, HN, hc0, tpos0, tcnt0, tknown0, tce_hosts, tce_hosts_g);
+            if (bs != KP_OK) return bs;
         }
         if (tcl.empty()) tcl.push_back(0);
         if (trl.empty()) trl.push_back(0);
@@ -2889,22 +2985,22 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
         // TopoSnap rows the FFD kernel's LDS plan holds: the most constraining groups of any class (at most KP_SNAP_ROWS)
         d.snap_rows = 1;
         for (int i = 0; i < C && G > 0; i++)
-            d.snap_rows = std::max(d.snap_rows, std::min((int)th.cons[i].size(), (int)KP_SNAP_ROWS));
-        c->tg_nlate = G > 0 ? th.n_late : 0;
+            d.snap_rows = std::max(d.snap_rows, std::min((int)se.th.cons[i].size(), (int)KP_SNAP_ROWS));
+        c->tg_nlate = G > 0 ? se.th.n_late : 0;
         c->h_cls_birth.assign(std::max(C, 1), 0);
         d.born0 = 0;
         if (c->tg_nlate > 0) {
             HIPCHK(c->d_tg_late.upload(tlate, s));
-            c->h_cls_birth.assign(th.cls_birth.begin(), th.cls_birth.end());
+            c->h_cls_birth.assign(se.th.cls_birth.begin(), se.th.cls_birth.end());
             HIPCHK(c->d_cls_birth.upload(c->h_cls_birth, s));
             // NewTopology over the pods in input order: a variant is born only while no sibling is (topo_birth)
-            for (int i = 0; i < P; i++) d.born0 = late_birth(th.late_sib, d.born0, th.cls_birth[in->pods.class_id[i]]);
+            for (int i = 0; i < P; i++) d.born0 = late_birth(se.th.late_sib, d.born0, se.th.cls_birth[in->pods.class_id[i]]);
         }
-        c->tg_var = c->tg_nlate > 0 && th.any_var;
-        c->h_late_sib = th.late_sib;
+        c->tg_var = c->tg_nlate > 0 && se.th.any_var;
+        c->h_late_sib = se.th.late_sib;
         if (c->tg_var) {
-            HIPCHK(c->d_late_sib.upload(th.late_sib, s));
-            HIPCHK(c->d_late_grp.upload(th.late_grp, s));
+            HIPCHK(c->d_late_sib.upload(se.th.late_sib, s));
+            HIPCHK(c->d_late_grp.upload(se.th.late_grp, s));
         }
         HIPCHK(c->d_tg_cnt0.upload(tcnt0, s));
         HIPCHK(c->d_tg_cnt.ensure(tcnt0.size()));
@@ -2921,12 +3017,27 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
         HIPCHK(c->d_vrank.upload(vrank, s));
         d.HN = HN;
     }
-    if (P > 0) {
+    return KP_OK;
+}
+
+static kp_status solve_sort_workspace(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    if (in->pods.n_pods > 0) {
         size_t tb = 0;
-        HIPCHK(kp_queue_sort(nullptr, P, c->d_perm_a.p, c->d_perm_b.p, c->d_keys_a.p, c->d_keys_b.p, nullptr, &tb, s, nullptr));
-        HIPCHK(c->d_sort_temp.ensure(tb));
-        c->sort_temp_bytes = tb;
+        HIPCHK(kp_queue_sort(nullptr, in->pods.n_pods, ctx->d_perm_a.p, ctx->d_perm_b.p, ctx->d_keys_a.p, ctx->d_keys_b.p, nullptr, &tb,
+                             ctx->stream, nullptr));
+        HIPCHK(ctx->d_sort_temp.ensure(tb));
+        ctx->sort_temp_bytes = tb;
     }
+    return KP_OK;
+}
+
+#define DEV(x) d.x = c->d_##x.p  // the KpDev member named after the ctx buffer
+static kp_status solve_fill_dev(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    kp_ctx* c = ctx;
+    const int T = c->T, TW = c->TW, R = c->R, P = in->pods.n_pods, C = in->n_classes, G = c->tg_G;
+    const int E = se.E, EW = se.EW, NT = se.NT, K = se.K, DW = se.DW, NCcap = se.NCcap, M = se.M;
+    hipStream_t s = c->stream;
+    KpDev& d = c->dev;
     // ---- KpDev ----
     d.T = T;
     d.TW = TW;
@@ -2934,28 +3045,11 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     d.K = K;
     d.n_slots = c->n_slots;
     d.n_multi = c->n_multi;
-    d.type_val = c->d_type_val.p;
-    d.multi_mask = c->d_multi_mask.p;
+    DEV(type_val); DEV(multi_mask);
     d.multi16 = c->multi16_ok ? c->d_multi16.p : nullptr;
-    d.dne_mask = c->d_dne_mask.p;
-    d.alloc = c->d_alloc.p;
-    d.cap = c->d_cap.p;
-    d.avail_zc = c->d_avail_zc.p;
-    d.slot_price = c->d_slot_price.p;
-    d.slot_zone = c->d_slot_zone.p;
-    d.slot_ct = c->d_slot_ct.p;
-    d.slot_zoneid = c->d_slot_zoneid.p;
-    d.name_rank = c->d_name_rank.p;
-    d.nonneg = c->d_nonneg.p;
-    d.kflags = c->d_kflags.p;
-    d.kcat = c->d_kcat.p;
-    d.kmulti = c->d_kmulti.p;
-    d.woff = c->d_woff.p;
-    d.nw = c->d_nw.p;
-    d.nval = c->d_nval.p;
-    d.vbase = c->d_vbase.p;
-    d.val_isint = c->d_val_isint.p;
-    d.val_int = c->d_val_int.p;
+    DEV(dne_mask); DEV(alloc); DEV(cap); DEV(avail_zc); DEV(slot_price); DEV(slot_zone); DEV(slot_ct); DEV(slot_zoneid);
+    DEV(name_rank); DEV(nonneg); DEV(kflags); DEV(kcat); DEV(kmulti); DEV(woff); DEV(nw); DEV(nval); DEV(vbase);
+    DEV(val_isint); DEV(val_int);
     d.DW = DW;
     d.key_zone = c->key_zone;
     d.key_ct = c->key_ct;
@@ -2964,41 +3058,17 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     d.key_resvtype = c->key_resvtype;
     d.C = C;
     d.NT = NT;
-    d.cls_koff = c->d_cls_koff.p;
-    d.cls_keys = c->d_cls_keys.p;
-    d.cls_wsoff = c->d_cls_wsoff.p;
-    d.cls_hdr = c->d_cls_hdr.p;
-    d.cls_words = c->d_cls_words.p;
-    d.cls_flags = c->d_cls_flags.p;
-    d.V = c->d_V.p;
-    d.tmpl_rows = c->d_tmpl_rows.p;
-    d.tmpl_opts = c->d_tmpl_opts.p;
-    d.tmpl_ok = c->d_tmpl_ok.p;
-    d.tol = c->d_tol.p;
-    d.daemon = c->d_daemon.p;
-    d.limit_set = c->d_limit_set.p;
-    d.remaining = c->d_remaining.p;
+    DEV(cls_koff); DEV(cls_keys); DEV(cls_wsoff); DEV(cls_hdr); DEV(cls_words); DEV(cls_flags); DEV(V); DEV(tmpl_rows);
+    DEV(tmpl_opts); DEV(tmpl_ok); DEV(tol); DEV(daemon); DEV(limit_set); DEV(remaining);
     HIPCHK(c->d_tmpl_lmask.ensure((size_t)std::max(1, d.NT) * std::max(1, d.TW)));
-    d.tmpl_lmask = c->d_tmpl_lmask.p;
-    d.min_keys = c->d_min_keys.p;
+    DEV(tmpl_lmask); DEV(min_keys);
     d.E = E;
     d.EW = EW;
-    d.ex_hdr0 = c->d_ex_hdr0.p;
-    d.ex_words0 = c->d_ex_words0.p;
-    d.ex_hdr = c->d_ex_hdr.p;
-    d.ex_words = c->d_ex_words.p;
-    d.ex_avail = c->d_ex_avail.p;
-    d.ex_req = c->d_ex_req.p;
-    d.ex_head = c->d_ex_head.p;
-    d.ex_static = c->d_ex_static.p;
-    d.XT = c->d_XT.p;
-    d.ex_tol = c->d_ex_tol.p;
-    d.cls_xkoff = c->d_cls_xkoff.p;
-    d.cls_xkeys = c->d_cls_xkeys.p;
-    d.ex_mayfix = mayfix ? 1 : 0;
+    DEV(ex_hdr0); DEV(ex_words0); DEV(ex_hdr); DEV(ex_words); DEV(ex_avail); DEV(ex_req); DEV(ex_head); DEV(ex_static);
+    DEV(XT); DEV(ex_tol); DEV(cls_xkoff); DEV(cls_xkeys);
+    d.ex_mayfix = se.mayfix ? 1 : 0;
     d.P = P;
-    d.pod_cls = c->d_pod_cls.p;
-    d.pod_shape = c->d_pod_shape.p;
+    DEV(pod_cls); DEV(pod_shape);
     const bool relax = !c->pref.relax_next.empty();
     d.relax_next = relax ? c->d_relax_next.p : nullptr;
     d.shape_next = relax ? c->d_shape_next.p : nullptr;
@@ -3006,73 +3076,23 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     d.pod_shape0 = relax ? c->d_pod_shape0.p : nullptr;
     d.last_ep = relax ? c->d_last_ep.p : nullptr;
     d.best_effort = c->best_effort ? 1 : 0;
-    d.pod_req = c->d_pod_req.p;
+    DEV(pod_req);
     d.queue0 = nullptr;  // set by execute (sort output)
     d.NCcap = NCcap;
-    d.nc_hdr = c->d_nc_hdr.p;
-    d.nc_words = c->d_nc_words.p;
-    d.nc_opts = c->d_nc_opts.p;
-    d.nc_req = c->d_nc_req.p;
-    d.nc_tmpl = c->d_nc_tmpl.p;
-    d.empty_hdr = c->d_empty_hdr.p;
-    d.empty_words = c->d_empty_words.p;
-    d.qbuf = c->d_qbuf.p;
-    d.last_len = c->d_last_len.p;
-    d.pod_result = c->d_pod_result.p;
-    d.pod_order = c->d_pod_order.p;
-    d.nc_count = c->d_nc_count.p;
-    d.nc_npods = c->d_nc_npods.p;
-    d.nc_slice_pos = c->d_nc_slice_pos.p;
-    d.nc_nopts = c->d_nc_nopts.p;
-    d.nc_valid = c->d_nc_valid.p;
+    DEV(nc_hdr); DEV(nc_words); DEV(nc_opts); DEV(nc_req); DEV(nc_tmpl); DEV(empty_hdr); DEV(empty_words); DEV(qbuf);
+    DEV(last_len); DEV(pod_result); DEV(pod_order); DEV(nc_count); DEV(nc_npods); DEV(nc_slice_pos); DEV(nc_nopts);
+    DEV(nc_valid);
     d.M = M;
-    d.nc_types = c->d_nc_types.p;
-    d.nc_ntypes = c->d_nc_ntypes.p;
-    d.stats = c->d_stats.p;
-    d.err = c->d_err.p;
-    d.profile = getenv("KPSIM_PROFILE") ? 1 : 0;
-    // topology pods: candidates per block round (KPSIM_TOPO_CANDS, diagnostics)
-    {  // topology solves run the KP_NWAVES_TOPO-wave instantiations
-        const int nw = G > 0 ? KP_NWAVES_TOPO : KP_NWAVES;
-        d.topo_cands = getenv("KPSIM_TOPO_CANDS") ? std::max(1, std::min(nw, atoi(getenv("KPSIM_TOPO_CANDS")))) : nw;
-    }
-    d.team_eval = getenv("KPSIM_NO_TEAM") ? 0 : 1;  // diagnostics: KPSIM_NO_TEAM=1 evaluates topology candidates one per wave
-    d.noop_quick = getenv("KPSIM_NO_NOOP") ? 0 : 1;  // diagnostics: KPSIM_NO_NOOP=1 disables the no-op merge quick accept
-    d.team_first = getenv("KPSIM_NO_TEAM_FIRST") ? 0 : 1;  // diagnostics: KPSIM_NO_TEAM_FIRST=1 evaluates it beside the others
-    d.block_sort = getenv("KPSIM_NO_BLOCK_SORT") ? 0 : 1;  // diagnostics: KPSIM_NO_BLOCK_SORT=1 leaves it to wave 0
-    // KPSIM_TRACE_POD=p traces pod p; KPSIM_TRACE_CLASS=c traces every slow-path pod of class c (trace_pod = -2 - c)
-    d.trace_pod = getenv("KPSIM_TRACE_POD") ? atoi(getenv("KPSIM_TRACE_POD"))
-                  : getenv("KPSIM_TRACE_CLASS") ? -2 - atoi(getenv("KPSIM_TRACE_CLASS")) : -1;
-    d.trace_max = getenv("KPSIM_TRACE_MAXPOD") ? atoi(getenv("KPSIM_TRACE_MAXPOD")) : INT32_MAX;
-    d.trace = nullptr;
-    if (d.trace_pod != -1) {
-        HIPCHK(c->d_trace.ensure(1 + 6 * KP_TRACE_N + 3 + 2 * 4096));
-        d.trace = c->d_trace.p;
-    }
+    DEV(nc_types); DEV(nc_ntypes); DEV(stats); DEV(err);
     d.G = G;
-    d.key_host = th.key_host;
-    d.tg_info = c->d_tg_info.p;
-    d.tg_hrow = c->d_tg_hrow.p;
-    d.tg_owner = c->d_tg_owner.p;
-    d.tg_pol = c->d_tg_pol.p;
-    d.tg_frow = c->d_tg_frow.p;
+    d.key_host = se.th.key_host;
+    DEV(tg_info); DEV(tg_hrow); DEV(tg_owner); DEV(tg_pol); DEV(tg_frow);
     d.tg_late = c->tg_nlate > 0 ? c->d_tg_late.p : nullptr;
     d.cls_birth = c->tg_nlate > 0 ? c->d_cls_birth.p : nullptr;
     d.late_sib = c->tg_var ? c->d_late_sib.p : nullptr;
     d.late_grp = c->tg_var ? c->d_late_grp.p : nullptr;
-    d.tg_cnt = c->d_tg_cnt.p;
-    d.tg_known = c->d_tg_known.p;
-    d.tg_hcnt = c->d_tg_hcnt.p;
-    d.tg_pos = c->d_tg_pos.p;
-    d.cls_tcoff = c->d_cls_tcoff.p;
-    d.cls_tc = c->d_cls_tc.p;
-    d.cls_troff = c->d_cls_troff.p;
-    d.cls_tr = c->d_cls_tr.p;
-    d.cls_tce = c->d_cls_tce.p;
-    d.tce_hosts = c->d_tce_hosts.p;
-    d.cls_tre = c->d_cls_tre.p;
-    d.cls_kneutral = c->d_cls_kneutral.p;
-    d.vrank = c->d_vrank.p;
+    DEV(tg_cnt); DEV(tg_known); DEV(tg_hcnt); DEV(tg_pos); DEV(cls_tcoff); DEV(cls_tc); DEV(cls_troff); DEV(cls_tr);
+    DEV(cls_tce); DEV(tce_hosts); DEV(cls_tre); DEV(cls_kneutral); DEV(vrank);
     // quick-accept headroom scale per active axis: every allocatable value >> qshift fits in 30 bits
     for (int ai = 0; ai < KP_LDS_AXES; ai++) {
         int sh = 0;
@@ -3084,16 +3104,13 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
         d.qshift[ai] = sh;
     }
     d.ro = c->h_ro.n > 0 ? c->d_ro.p : nullptr;
-    d.type_ro = c->d_type_ro.p;
-    d.ro_price = c->d_ro_price.p;
+    DEV(type_ro); DEV(ro_price);
     d.ro_n = c->h_ro.n;
     d.ro_w = c->h_ro.w;
     d.ro_nrid = c->h_ro.nrid;
     d.ro_ridw = c->h_ro.ridw;
     d.resv_on = (c->reserved_capacity && c->h_ro.n > 0) ? 1 : 0;
-    d.rcap0 = c->d_rcap0.p;
-    d.nc_held = c->d_nc_held.p;
-    d.nc_rlive = c->d_nc_rlive.p;
+    DEV(rcap0); DEV(nc_held); DEV(nc_rlive);
     d.alloc_act = nullptr;
     if (NCcap > KP_NC_FIRST || T > 1024) {  // node-dense plan or large catalog: the staged axes' allocatable table in HBM
                                             // ([axes][TP], TP = 64-padded T) when LDS cannot hold it
@@ -3108,29 +3125,101 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
         HIPCHK(c->d_g_ord.ensure(NCcap));
         HIPCHK(c->d_g_last.ensure(NCcap));
         HIPCHK(c->d_g_tmpl.ensure(NCcap));
-        d.g_key = c->d_g_key.p;
-        d.g_ord = c->d_g_ord.p;
-        d.g_last = c->d_g_last.p;
-        d.g_tmpl = c->d_g_tmpl.p;
+        DEV(g_key); DEV(g_ord); DEV(g_last); DEV(g_tmpl);
     }
+    return KP_OK;
+}
+#undef DEV
+
+// The KPSIM_* diagnostics switches of the Solve, read on every call (tests set them between calls in one process).
+static kp_status solve_diag_switches(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    KpDev& d = ctx->dev;
+    d.profile = getenv("KPSIM_PROFILE") ? 1 : 0;
+    // topology pods: candidates per block round (KPSIM_TOPO_CANDS, diagnostics)
+    {  // topology solves run the KP_NWAVES_TOPO-wave instantiations
+        const int nw = ctx->tg_G > 0 ? KP_NWAVES_TOPO : KP_NWAVES;
+        d.topo_cands = getenv("KPSIM_TOPO_CANDS") ? std::max(1, std::min(nw, atoi(getenv("KPSIM_TOPO_CANDS")))) : nw;
+    }
+    d.team_eval = getenv("KPSIM_NO_TEAM") ? 0 : 1;  // diagnostics: KPSIM_NO_TEAM=1 evaluates topology candidates one per wave
+    d.noop_quick = getenv("KPSIM_NO_NOOP") ? 0 : 1;  // diagnostics: KPSIM_NO_NOOP=1 disables the no-op merge quick accept
+    d.team_first = getenv("KPSIM_NO_TEAM_FIRST") ? 0 : 1;  // diagnostics: KPSIM_NO_TEAM_FIRST=1 evaluates it beside the others
+    d.block_sort = getenv("KPSIM_NO_BLOCK_SORT") ? 0 : 1;  // diagnostics: KPSIM_NO_BLOCK_SORT=1 leaves it to wave 0
+    // KPSIM_TRACE_POD=p traces pod p; KPSIM_TRACE_CLASS=c traces every slow-path pod of class c (trace_pod = -2 - c)
+    d.trace_pod = getenv("KPSIM_TRACE_POD") ? atoi(getenv("KPSIM_TRACE_POD"))
+                  : getenv("KPSIM_TRACE_CLASS") ? -2 - atoi(getenv("KPSIM_TRACE_CLASS")) : -1;
+    d.trace_max = getenv("KPSIM_TRACE_MAXPOD") ? atoi(getenv("KPSIM_TRACE_MAXPOD")) : INT32_MAX;
+    d.trace = nullptr;
+    if (d.trace_pod != -1) {
+        HIPCHK(ctx->d_trace.ensure(1 + 6 * KP_TRACE_N + 3 + 2 * 4096));
+        d.trace = ctx->d_trace.p;
+    }
+    return KP_OK;
+}
+
+
+static kp_status solve_plan_lds(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    KpDev& d = ctx->dev;
     if (!kp_ffd_plan_lds(d, KP_LDS_BYTES)) return fail(ctx, KP_E_UNSUPPORTED, "FFD kernel LDS plan exceeds 160 KB");
-    if (getenv("KPSIM_PROFILE"))
+    if (d.profile)  // KPSIM_PROFILE (solve_diag_switches)
         fprintf(stderr, "[kpsim] FFD LDS plan: fixed block %zu B, quick rows %d (axes %d), NodeClaim slots %d, allocatable %s, "
                 "%d B of %d\n", d.G > 0 ? kp_ffd_shared_bytes_topo() : kp_ffd_shared_bytes(), d.lds_nq, d.lds_A, d.lds_ncmax, d.alloc_global ? "HBM" : "LDS",
                 d.lds_bytes, KP_LDS_BYTES);
-    c->P = P;
-    c->C = C;
-    c->NT = NT;
-    c->K = K;
-    c->DW = DW;
-    c->M = M;
-    HIPCHK(hipStreamSynchronize(s));
+    return KP_OK;
+}
+
+#define STAGE(f) if (const kp_status _s = f(ctx, in, se); _s != KP_OK) return _s
+extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try {
+    g_prep_t = std::chrono::steady_clock::now();
+    if (!ctx || !in) return KP_E_INVALID;
+    ctx->cons_prep_valid = false;
+    ctx->cons_gen++;  // cached pass rows and read-backs of kp_consolidate_command are stale
+    if (!ctx->have_catalog) return fail(ctx, KP_E_STATE, "kp_solve before kp_catalog_upload");
+    if (!ctx->solve_unsupported.empty()) return fail(ctx, KP_E_UNSUPPORTED, "Solve: " + ctx->solve_unsupported);
+    if (ctx->has_reserved && !ctx->ro_ok)
+        return fail(ctx, KP_E_UNSUPPORTED, "Solve over this catalog: " + ctx->ro_why);
+    const auto t0 = clk::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    kp_ctx* c = ctx;
+    c->prepared = c->executed = false;
+    c->cons_prepared = false;
+    SolveEnc se;
+    STAGE(solve_expand);
+    in = &c->pref.in;  // from here on: the expanded classes (stage 0 of input class i is class i)
+    PREP_MARK(0);
+    STAGE(solve_class_reqs);
+    STAGE(solve_templates);
+    STAGE(solve_topology_groups);
+    STAGE(solve_existing);
+    STAGE(solve_key_layout);
+    PREP_MARK(1);
+    STAGE(solve_digests);
+    STAGE(solve_template_tables);
+    STAGE(solve_existing_digests);
+    PREP_MARK(2);
+    STAGE(solve_pods);  // PREP_MARK(3) sits inside, between the pod passes and shape_next.  Resets ctx->dev and sets its
+                        // active axes; solve_topology_tables adds snap_rows, born0 and HN; solve_fill_dev the rest
+    PREP_MARK(4);
+    STAGE(solve_upload);
+    STAGE(solve_plan_nodeclaims);
+    STAGE(solve_topology_tables);
+    STAGE(solve_sort_workspace);
+    STAGE(solve_fill_dev);
+    STAGE(solve_diag_switches);
+    STAGE(solve_plan_lds);
+    c->P = in->pods.n_pods;
+    c->C = in->n_classes;
+    c->NT = se.NT;
+    c->K = se.K;
+    c->DW = se.DW;
+    c->M = se.M;
+    HIPCHK(hipStreamSynchronize(c->stream));
     c->ns_prep = ns_since(t0);
     c->prepared = true;
     return KP_OK;
 } catch (const std::exception& e) {
     return fail(ctx, KP_E_INVALID, e.what());
 }
+#undef STAGE
 
 // ---------------------------------------------------------------------------------------------
 // solve: execute (device only)
@@ -3403,6 +3492,156 @@ extern "C" int32_t kp_consolidate_probe_count(const kp_consolidate_input* in) {
     return nm + ns;  // KP_CONSOLIDATE_BOTH
 }
 
+// inputs: candidates on distinct nodes, each pod pending or owned by one candidate, prices >= 0
+static kp_status cons_check_inputs(kp_ctx* ctx, const kp_consolidate_input* in) {
+    const int P = in->cluster.pods.n_pods, E = in->cluster.n_existing, NC = in->n_candidates;
+    std::vector<uint8_t> seen_pod(std::max(P, 1), 0), seen_node(std::max(E, 1), 0);
+    for (int i = 0; i < in->n_pending; i++) {
+        const int p = in->pending[i];
+        if (p < 0 || p >= P || seen_pod[p]++) return fail(ctx, KP_E_INVALID, "pending pod out of range or repeated");
+    }
+    for (int ci = 0; ci < NC; ci++) {
+        const kp_candidate& cd = in->candidates[ci];
+        if (cd.node < 0 || cd.node >= E || seen_node[cd.node]++) return fail(ctx, KP_E_INVALID, "candidate node out of range or repeated");
+        if (!(cd.price >= 0) || cd.price > DBL_MAX) return fail(ctx, KP_E_INVALID, "candidate price must be finite and >= 0");
+        if (cd.n_pods < 0 || (cd.n_pods > 0 && !cd.pods)) return fail(ctx, KP_E_INVALID, "candidate pods");
+        for (int i = 0; i < cd.n_pods; i++) {
+            const int p = cd.pods[i];
+            if (p < 0 || p >= P || seen_pod[p]++) return fail(ctx, KP_E_INVALID, "candidate pod out of range or repeated");
+        }
+    }
+    return KP_OK;
+}
+
+// topology: the starting decrements of every probe — single-node probe ci: candidate ci's rows; multi-node probe i:
+// the sum over candidates [0, i + 2) — one row of 64 value counts per group
+static kp_status cons_topology_decrements(kp_ctx* ctx, const kp_consolidate_input* in) {
+    const int NC = in->n_candidates;
+    hipStream_t s = ctx->stream;
+    KpCons& k = ctx->cons;
+    std::vector<int32_t> soff(NC + 1, 0), dg, dv;
+    for (int ci = 0; ci < NC; ci++) {
+        for (auto& kv : ctx->cons_dec[ci]) {
+            dg.push_back(kv.first);
+            dv.insert(dv.end(), kv.second.begin(), kv.second.end());
+        }
+        soff[ci + 1] = (int32_t)dg.size();
+    }
+    const int mx = ctx->cons_max_candidates;
+    const int nm = NC < 2 ? 0 : (NC <= mx ? NC - 1 : mx);
+    std::vector<int32_t> moff(nm + 1, (int32_t)dg.size());
+    std::map<int, std::vector<int32_t>> acc;
+    auto add = [&](int ci) {
+        for (auto& kv : ctx->cons_dec[ci]) {
+            auto& row = acc[kv.first];
+            if (row.empty()) row.assign(64, 0);
+            for (int v = 0; v < 64; v++) row[v] += kv.second[v];
+        }
+    };
+    for (int i = 0; i < nm; i++) {
+        if (i == 0) add(0);
+        add(i + 1);
+        for (auto& kv : acc) {
+            dg.push_back(kv.first);
+            dv.insert(dv.end(), kv.second.begin(), kv.second.end());
+        }
+        moff[i + 1] = (int32_t)dg.size();
+    }
+    if (dg.empty()) {
+        dg.push_back(0);
+        dv.assign(64, 0);
+    }
+    HIPCHK(ctx->d_dec_soff.upload(soff, s));
+    HIPCHK(ctx->d_dec_moff.upload(moff, s));
+    HIPCHK(ctx->d_dec_g.upload(dg, s));
+    HIPCHK(ctx->d_dec_v.upload(dv, s));
+    HIPCHK(ctx->d_pt_dgk.upload(ctx->h_tknown_dg, s));
+    // hostname pod affinity: each probe's positive-domain count per group (the base minus the domains only its
+    // candidates' pods held)
+    std::vector<int32_t> ha(k.G, -1), hg;
+    for (int gi = 0; gi < k.G; gi++)
+        if (ctx->tg_host_aff[gi]) {
+            ha[gi] = (int)hg.size();
+            hg.push_back(gi);
+        }
+    k.n_ha = (int)hg.size();
+    std::vector<int32_t> hp((size_t)std::max(1, (NC + nm) * k.n_ha), 0);
+    if (k.n_ha > 0) {
+        std::vector<int32_t> acc(k.n_ha, 0);
+        for (int ci = 0; ci < NC; ci++) {
+            for (int ga = 0; ga < k.n_ha; ga++) hp[(size_t)ci * k.n_ha + ga] = ctx->h_tpos0[hg[ga]];
+            for (int g : ctx->cons_hlost[ci]) hp[(size_t)ci * k.n_ha + ha[g]]--;
+        }
+        for (int i = 0; i < nm; i++) {  // multi-node probe i: candidates [0, i + 2)
+            for (int cc = i == 0 ? 0 : i + 1; cc < i + 2; cc++)
+                for (int g : ctx->cons_hlost[cc]) acc[ha[g]]++;
+            for (int ga = 0; ga < k.n_ha; ga++) hp[(size_t)(NC + i) * k.n_ha + ga] = ctx->h_tpos0[hg[ga]] - acc[ga];
+        }
+    }
+    HIPCHK(ctx->d_tg_ha.upload(ha, s));
+    HIPCHK(ctx->d_hpos0.upload(hp, s));
+    return KP_OK;
+}
+
+// mutators (kp_solve_prepare): a probe that reschedules a pod whose class, or a relaxation stage of it, may change a
+// node's requirements runs on the MUT variant (per-probe node requirement copies); the others are unaffected
+static kp_status cons_mutators(kp_ctx* ctx, const kp_consolidate_input* in) {
+    const int NC = in->n_candidates;
+    hipStream_t s = ctx->stream;
+    KpCons& k = ctx->cons;
+    const kp_solve_input& cl = in->cluster;
+    const int C0 = cl.n_classes;
+    std::vector<uint8_t> chain(std::max(C0, 1), 0);
+    for (int i = 0; i < C0; i++)
+        for (int s = i; s >= 0 && !chain[i]; s = ctx->pref.relax_next.empty() ? -1 : ctx->pref.relax_next[s])
+            if (s < (int)ctx->cons_mutcls.size() && ctx->cons_mutcls[s]) chain[i] = 1;
+    auto pod_mut = [&](int p) { return chain[cl.pods.class_id[p]] != 0; };
+    bool pend_mut = false;
+    for (int i = 0; i < in->n_pending; i++) pend_mut = pend_mut || pod_mut(in->pending[i]);
+    const int mx = ctx->cons_max_candidates;
+    const int nm = NC < 2 ? 0 : (NC <= mx ? NC - 1 : mx);
+    std::vector<int32_t> ms(std::max(NC, 1), 0), mm(std::max(nm, 1), 0);
+    int any = 0, pre = pend_mut ? 1 : 0;
+    for (int ci = 0; ci < NC; ci++) {
+        int f = pend_mut ? 1 : 0;
+        for (int q = 0; q < in->candidates[ci].n_pods && !f; q++) f = pod_mut(in->candidates[ci].pods[q]) ? 1 : 0;
+        ms[ci] = f;
+        any |= f;
+        pre |= f;  // multi-node probe i covers candidates [0, i + 2)
+        if (ci >= 1 && ci - 1 < nm) mm[ci - 1] = pre;
+    }
+    k.mut = any;
+    ctx->cons_n_mut = 0;
+    for (int ci = 0; ci < NC; ci++) ctx->cons_n_mut += ms[ci];
+    for (int i = 0; i < nm; i++) ctx->cons_n_mut += mm[i];
+    HIPCHK(ctx->d_mut_s.upload(ms, s));
+    HIPCHK(ctx->d_mut_m.upload(mm, s));
+    // late topology identities a probe's NewTopology creates: owned by its pending pods or its candidates' pods
+    k.born_s = k.born_m = nullptr;
+    if (ctx->tg_nlate > 0) {
+        // in the probe's pod order (pending, then its candidates' pods): a variant is born only while no sibling
+        // is, so each probe starts with its own first owner's variant
+        const std::vector<uint64_t>& sib = ctx->tg_var ? ctx->h_late_sib : std::vector<uint64_t>();
+        uint64_t bp = 0;
+        for (int i = 0; i < in->n_pending; i++) bp = late_birth(sib, bp, ctx->h_cls_birth[cl.pods.class_id[in->pending[i]]]);
+        std::vector<uint64_t> bs(std::max(NC, 1), bp), bm(std::max(nm, 1), bp);
+        uint64_t acc = bp;
+        for (int ci = 0; ci < NC; ci++) {
+            for (int q = 0; q < in->candidates[ci].n_pods; q++) {
+                const uint64_t cb = ctx->h_cls_birth[cl.pods.class_id[in->candidates[ci].pods[q]]];
+                bs[ci] = late_birth(sib, bs[ci], cb);
+                acc = late_birth(sib, acc, cb);
+            }
+            if (ci >= 1 && ci - 1 < nm) bm[ci - 1] = acc;  // multi-node probe i covers candidates [0, i + 2)
+        }
+        HIPCHK(ctx->d_born_s.upload(bs, s));
+        HIPCHK(ctx->d_born_m.upload(bm, s));
+        k.born_s = ctx->d_born_s.p;
+        k.born_m = ctx->d_born_m.p;
+    }
+    return KP_OK;
+}
+
 static kp_status cons_prepare_one(kp_ctx* ctx, const kp_consolidate_input* in) try {
     if (!ctx || !in) return KP_E_INVALID;
     ctx->cons_prepared = false;
@@ -3415,24 +3654,7 @@ static kp_status cons_prepare_one(kp_ctx* ctx, const kp_consolidate_input* in) t
         return fail(ctx, KP_E_INVALID, "unknown consolidation mode");
     const kp_solve_input& cl = in->cluster;
     const int P = cl.pods.n_pods, E = cl.n_existing, NC = in->n_candidates;
-    // inputs: candidates on distinct nodes, each pod pending or owned by one candidate, prices >= 0
-    {
-        std::vector<uint8_t> seen_pod(std::max(P, 1), 0), seen_node(std::max(E, 1), 0);
-        for (int i = 0; i < in->n_pending; i++) {
-            const int p = in->pending[i];
-            if (p < 0 || p >= P || seen_pod[p]++) return fail(ctx, KP_E_INVALID, "pending pod out of range or repeated");
-        }
-        for (int ci = 0; ci < NC; ci++) {
-            const kp_candidate& cd = in->candidates[ci];
-            if (cd.node < 0 || cd.node >= E || seen_node[cd.node]++) return fail(ctx, KP_E_INVALID, "candidate node out of range or repeated");
-            if (!(cd.price >= 0) || cd.price > DBL_MAX) return fail(ctx, KP_E_INVALID, "candidate price must be finite and >= 0");
-            if (cd.n_pods < 0 || (cd.n_pods > 0 && !cd.pods)) return fail(ctx, KP_E_INVALID, "candidate pods");
-            for (int i = 0; i < cd.n_pods; i++) {
-                const int p = cd.pods[i];
-                if (p < 0 || p >= P || seen_pod[p]++) return fail(ctx, KP_E_INVALID, "candidate pod out of range or repeated");
-            }
-        }
-    }
+    if (const kp_status st = cons_check_inputs(ctx, in); st != KP_OK) return st;
     // topology: every candidate's reschedulable pods are bound to its node in the cluster (base counts); kp_solve_prepare
     // also keeps each candidate's value-keyed contributions (cons_dec) so that a probe takes off the pods it reschedules
     ctx->cons_extra.clear();
@@ -3516,126 +3738,11 @@ static kp_status cons_prepare_one(kp_ctx* ctx, const kp_consolidate_input* in) t
     HIPCHK(c->d_cand_cap.upload(ccap, s));
     HIPCHK(c->d_init.upload(init, s));
     HIPCHK(c->d_alloc_act.upload(act, s));
-    // topology: the starting decrements of every probe — single-node probe ci: candidate ci's rows; multi-node probe i:
-    // the sum over candidates [0, i + 2) — one row of 64 value counts per group
     k.G = c->tg_G;
     k.HG = c->tg_HG;
-    if (k.G > 0) {
-        std::vector<int32_t> soff(NC + 1, 0), dg, dv;
-        for (int ci = 0; ci < NC; ci++) {
-            for (auto& kv : c->cons_dec[ci]) {
-                dg.push_back(kv.first);
-                dv.insert(dv.end(), kv.second.begin(), kv.second.end());
-            }
-            soff[ci + 1] = (int32_t)dg.size();
-        }
-        const int mx = c->cons_max_candidates;
-        const int nm = NC < 2 ? 0 : (NC <= mx ? NC - 1 : mx);
-        std::vector<int32_t> moff(nm + 1, (int32_t)dg.size());
-        std::map<int, std::vector<int32_t>> acc;
-        auto add = [&](int ci) {
-            for (auto& kv : c->cons_dec[ci]) {
-                auto& row = acc[kv.first];
-                if (row.empty()) row.assign(64, 0);
-                for (int v = 0; v < 64; v++) row[v] += kv.second[v];
-            }
-        };
-        for (int i = 0; i < nm; i++) {
-            if (i == 0) add(0);
-            add(i + 1);
-            for (auto& kv : acc) {
-                dg.push_back(kv.first);
-                dv.insert(dv.end(), kv.second.begin(), kv.second.end());
-            }
-            moff[i + 1] = (int32_t)dg.size();
-        }
-        if (dg.empty()) {
-            dg.push_back(0);
-            dv.assign(64, 0);
-        }
-        HIPCHK(c->d_dec_soff.upload(soff, s));
-        HIPCHK(c->d_dec_moff.upload(moff, s));
-        HIPCHK(c->d_dec_g.upload(dg, s));
-        HIPCHK(c->d_dec_v.upload(dv, s));
-        HIPCHK(c->d_pt_dgk.upload(c->h_tknown_dg, s));
-        // hostname pod affinity: each probe's positive-domain count per group (the base minus the domains only its
-        // candidates' pods held)
-        std::vector<int32_t> ha(k.G, -1), hg;
-        for (int gi = 0; gi < k.G; gi++)
-            if (c->tg_host_aff[gi]) {
-                ha[gi] = (int)hg.size();
-                hg.push_back(gi);
-            }
-        k.n_ha = (int)hg.size();
-        std::vector<int32_t> hp((size_t)std::max(1, (NC + nm) * k.n_ha), 0);
-        if (k.n_ha > 0) {
-            std::vector<int32_t> acc(k.n_ha, 0);
-            for (int ci = 0; ci < NC; ci++) {
-                for (int ga = 0; ga < k.n_ha; ga++) hp[(size_t)ci * k.n_ha + ga] = c->h_tpos0[hg[ga]];
-                for (int g : c->cons_hlost[ci]) hp[(size_t)ci * k.n_ha + ha[g]]--;
-            }
-            for (int i = 0; i < nm; i++) {  // multi-node probe i: candidates [0, i + 2)
-                for (int cc = i == 0 ? 0 : i + 1; cc < i + 2; cc++)
-                    for (int g : c->cons_hlost[cc]) acc[ha[g]]++;
-                for (int ga = 0; ga < k.n_ha; ga++) hp[(size_t)(NC + i) * k.n_ha + ga] = c->h_tpos0[hg[ga]] - acc[ga];
-            }
-        }
-        HIPCHK(c->d_tg_ha.upload(ha, s));
-        HIPCHK(c->d_hpos0.upload(hp, s));
-    }
-    // mutators (kp_solve_prepare): a probe that reschedules a pod whose class, or a relaxation stage of it, may change a
-    // node's requirements runs on the MUT variant (per-probe node requirement copies); the others are unaffected
-    {
-        const int C0 = cl.n_classes;
-        std::vector<uint8_t> chain(std::max(C0, 1), 0);
-        for (int i = 0; i < C0; i++)
-            for (int s = i; s >= 0 && !chain[i]; s = c->pref.relax_next.empty() ? -1 : c->pref.relax_next[s])
-                if (s < (int)c->cons_mutcls.size() && c->cons_mutcls[s]) chain[i] = 1;
-        auto pod_mut = [&](int p) { return chain[cl.pods.class_id[p]] != 0; };
-        bool pend_mut = false;
-        for (int i = 0; i < in->n_pending; i++) pend_mut = pend_mut || pod_mut(in->pending[i]);
-        const int mx = c->cons_max_candidates;
-        const int nm = NC < 2 ? 0 : (NC <= mx ? NC - 1 : mx);
-        std::vector<int32_t> ms(std::max(NC, 1), 0), mm(std::max(nm, 1), 0);
-        int any = 0, pre = pend_mut ? 1 : 0;
-        for (int ci = 0; ci < NC; ci++) {
-            int f = pend_mut ? 1 : 0;
-            for (int q = 0; q < in->candidates[ci].n_pods && !f; q++) f = pod_mut(in->candidates[ci].pods[q]) ? 1 : 0;
-            ms[ci] = f;
-            any |= f;
-            pre |= f;  // multi-node probe i covers candidates [0, i + 2)
-            if (ci >= 1 && ci - 1 < nm) mm[ci - 1] = pre;
-        }
-        k.mut = any;
-        c->cons_n_mut = 0;
-        for (int ci = 0; ci < NC; ci++) c->cons_n_mut += ms[ci];
-        for (int i = 0; i < nm; i++) c->cons_n_mut += mm[i];
-        HIPCHK(c->d_mut_s.upload(ms, s));
-        HIPCHK(c->d_mut_m.upload(mm, s));
-        // late topology identities a probe's NewTopology creates: owned by its pending pods or its candidates' pods
-        k.born_s = k.born_m = nullptr;
-        if (c->tg_nlate > 0) {
-            // in the probe's pod order (pending, then its candidates' pods): a variant is born only while no sibling
-            // is, so each probe starts with its own first owner's variant
-            const std::vector<uint64_t>& sib = c->tg_var ? c->h_late_sib : std::vector<uint64_t>();
-            uint64_t bp = 0;
-            for (int i = 0; i < in->n_pending; i++) bp = late_birth(sib, bp, c->h_cls_birth[cl.pods.class_id[in->pending[i]]]);
-            std::vector<uint64_t> bs(std::max(NC, 1), bp), bm(std::max(nm, 1), bp);
-            uint64_t acc = bp;
-            for (int ci = 0; ci < NC; ci++) {
-                for (int q = 0; q < in->candidates[ci].n_pods; q++) {
-                    const uint64_t cb = c->h_cls_birth[cl.pods.class_id[in->candidates[ci].pods[q]]];
-                    bs[ci] = late_birth(sib, bs[ci], cb);
-                    acc = late_birth(sib, acc, cb);
-                }
-                if (ci >= 1 && ci - 1 < nm) bm[ci - 1] = acc;  // multi-node probe i covers candidates [0, i + 2)
-            }
-            HIPCHK(c->d_born_s.upload(bs, s));
-            HIPCHK(c->d_born_m.upload(bm, s));
-            k.born_s = c->d_born_s.p;
-            k.born_m = c->d_born_m.p;
-        }
-    }
+    if (k.G > 0)
+        if (const kp_status st = cons_topology_decrements(ctx, in); st != KP_OK) return st;
+    if (const kp_status st = cons_mutators(ctx, in); st != KP_OK) return st;
     HIPCHK(c->d_next.ensure(3));
     HIPCHK(c->d_rank.ensure(std::max(P, 1)));
     HIPCHK(c->d_pend_bits.ensure(k.PW));
@@ -4458,6 +4565,193 @@ bool ireq_has(const kp_ctx* c, const IReq& q, int id, const char* name) {
 }
 }  // namespace
 
+// chunk-local tables of one encoding thread of kp_launch_select
+struct Chunk {
+    std::vector<KlKey> keys;
+    std::vector<KlMinKey> mins;
+    std::vector<uint64_t> words;
+    std::vector<IReq> scratch;
+    std::vector<uint8_t> constrained;
+    kp_status st = KP_OK;
+    std::string msg;
+};
+
+// One launch request encoded into its KlReq row and the chunk's key / minValues / word tables (offsets chunk-local).
+static bool launch_encode_one(kp_ctx* c, const kp_launch_request& lr, int i, Chunk& ch, const std::vector<uint8_t>& wk,
+                              const int* roles) {
+    const int R = c->R, Kc = c->Kcat;
+    KlReq* const reqs = c->p_l_req.p;
+    int64_t* const rq = c->p_l_rq.p;
+    std::vector<KlKey>& keys = ch.keys;
+    std::vector<KlMinKey>& mins = ch.mins;
+    std::vector<uint64_t>& words = ch.words;
+    auto err = [&](kp_status st, const char* m) {
+        ch.st = st;
+        ch.msg = m;
+        return false;
+    };
+    if (lr.n_requirements < 0 || (lr.n_requirements > 0 && !lr.requirements)) return err(KP_E_INVALID, "bad request");
+    // NewNodeSelectorRequirementsWithMinValues: Add = intersect per key, in catalog value-id space (values no type
+    // or offering carries are kept by name only: they decide whether a set is empty)
+    // ch.scratch holds reusable IReq slots: the first nm are this request's merged requirements
+    std::vector<IReq>& slots = ch.scratch;
+    size_t nm = 0;
+    for (int j = 0; j < lr.n_requirements; j++) {
+        const kp_requirement& r = lr.requirements[j];
+        if (!r.key || r.op < 0 || r.op > 5) return err(KP_E_INVALID, "bad requirement");
+        if (nm == slots.size()) slots.emplace_back();
+        IReq& q = slots[nm];
+        ireq_fill(c, r, q);
+        IReq* hit = nullptr;
+        for (size_t x = 0; x < nm; x++)
+            if (slots[x].kc == q.kc && (q.kc >= 0 || !strcmp(slots[x].name, q.name))) hit = &slots[x];
+        if (hit) {
+            ireq_norm(q);
+            ireq_norm(*hit);
+            *hit = ireq_intersection(c, q, *hit);
+        }
+        else nm++;
+    }
+    std::sort(slots.begin(), slots.begin() + nm, [](const IReq& a, const IReq& b) { return strcmp(a.name, b.name) < 0; });
+    struct View {  // the merged requirements of this request
+        const IReq* b;
+        const IReq* e;
+        const IReq* begin() const { return b; }
+        const IReq* end() const { return e; }
+    } m{slots.data(), slots.data() + nm};
+    if (lr.requests)
+        for (int r = 0; r < R; r++) rq[(size_t)i * R + r] = lr.requests[r];
+    KlReq& q = reqs[i];
+    q = KlReq{};
+    q.key_off = (int)keys.size();
+    int woff_of[KL_ROLES];
+    for (int r = 0; r < KL_ROLES; r++) woff_of[r] = -1;
+    const IReq* role_req[KL_ROLES] = {};
+    std::vector<uint8_t>& constrained = ch.constrained;
+    constrained.assign(Kc, 0);
+    for (const IReq& sq : m) {
+        const int kc = sq.kc;
+        if (kc < 0) continue;  // no type or offering carries the key: absent on both sides, never constrains
+        constrained[kc] = 1;
+        const KeyDict& kd = c->cat.keys[kc];
+        const int nv = (int)kd.vals.size();
+        const int woff = (int)words.size();
+        words.resize(words.size() + std::max<size_t>(1, (nv + 63) / 64), 0ull);
+        // bit v ⇔ Has(vals[v]); In sets visit only their own values, complements start full and clear theirs
+        if (!sq.comp) {
+            for (int v : sq.ids) words[woff + v / 64] |= 1ull << (v % 64);
+        } else {
+            const bool bounded = sq.has_gt || sq.has_lt;
+            for (int vv = 0; vv < nv; vv++)
+                if (!bounded || ireq_within(sq, kd.vals[vv])) words[woff + vv / 64] |= 1ull << (vv % 64);
+            for (int v : sq.ids) words[woff + v / 64] &= ~(1ull << (v % 64));
+        }
+        const int op = sq.op();
+        KlKey kk{kc, c->cat_multi[kc], 0u, woff};
+        kk.flags = (c->cat_kflags[kc] & KF_CAT_MULTI) ? KLK_MULTI : KLK_SINGLE;
+        if (op == 1 || op == 3) kk.flags |= KLK_DNE_OK;
+        if (c->cat_kflags[kc] != 0) keys.push_back(kk);
+        for (int r = 0; r < KL_ROLES; r++)
+            if (roles[r] == kc) {
+                woff_of[r] = woff;
+                role_req[r] = &sq;
+            }
+    }
+    q.n_keys = (int)keys.size() - q.key_off;
+    q.und_off = (int)keys.size();
+    for (int kc = 0; kc < Kc; kc++) {
+        if (c->cat_kflags[kc] == 0 || constrained[kc] || wk[kc]) continue;
+        KlKey kk{kc, c->cat_multi[kc], (c->cat_kflags[kc] & KF_CAT_MULTI) ? KLK_MULTI : KLK_SINGLE, 0};
+        keys.push_back(kk);
+    }
+    q.n_und = (int)keys.size() - q.und_off;
+    for (int r = 0; r < KL_ROLES; r++) {
+        const int kc = roles[r];
+        KlRole& ro = q.role[r];
+        ro = KlRole{KLR_PASS, 0u, 0, 0};
+        if (kc < 0) continue;
+        if (woff_of[r] >= 0) {
+            ro.mode = KLR_CONSTRAINED;
+            ro.woff = woff_of[r];
+            const int op = role_req[r]->op();
+            if (op == 1 || op == 3) ro.flags = KLK_DNE_OK;
+        } else if (!wk[kc]) {
+            ro.mode = KLR_FAIL_IN;
+        }
+    }
+    const IReq* ct = nullptr;
+    for (const IReq& x : m)
+        if (c->key_ct >= 0 ? x.kc == c->key_ct : !strcmp(x.name, "karpenter.sh/capacity-type")) ct = &x;
+    for (int x = 0; x < 3; x++) q.ct_has[x] = ct == nullptr ? 1 : (ireq_has(c, *ct, c->ct_vid[x], kCtNames[x]) ? 1 : 0);
+    q.min_off = (int)mins.size();
+    for (const IReq& sq : m) {
+        if (!sq.has_min) continue;
+        q.has_min = 1;
+        const int kc = sq.kc;
+        KlMinKey mk{-1, -1, 0, sq.minv};
+        if (kc >= 0 && c->cat_kflags[kc] != 0) {
+            mk.k = kc;
+            mk.mi = (c->cat_kflags[kc] & KF_CAT_MULTI) ? c->cat_multi[kc] : -1;
+            mk.nvals = (int)c->cat.keys[kc].vals.size();
+            if (mk.nvals > KP_MAX_MIN_WORDS * 64) return err(KP_E_UNSUPPORTED, "minValues key with > 4096 values");
+        } else {
+            mk.k = 0;  // no type carries the key: zero distinct values
+            mk.mi = -1;
+            mk.nvals = 0;
+            if (mk.minv > 0) mk.minv = INT32_MAX;
+        }
+        mins.push_back(mk);
+    }
+    q.n_min = (int)mins.size() - q.min_off;
+    return true;
+}
+
+// Result row i from the downloaded header, type list and override masks; its lists start at tp / op.
+static void launch_expand_row(const kp_ctx* c, int i, int M, int64_t tp, int64_t op, int64_t n_over, kp_launch_result& r,
+                              int32_t* type_ids, int32_t cap_type_ids, int32_t* override_offerings, int32_t cap_overrides) {
+    const int32_t* const h = c->p_l_hdr.p + (size_t)i * KL_HDR;
+    const int32_t* const tys = c->p_l_types.p;
+    const uint64_t* const ov = c->p_l_over.p;
+    r.status = h[0];
+    r.failed_filter = h[1];
+    r.capacity_type = h[2];
+    r.n_types = h[3];
+    r.n_options = h[5];
+    for (int f = 0; f < KP_N_FILTERS; f++) r.rejected[f] = h[8 + f];
+    r.type_offset = (int32_t)tp;
+    r.override_offset = (int32_t)op;
+    r.n_overrides = (int32_t)n_over;
+    // kwok CreateFleet's lowest-price pick (kpsim.h kp_launch_result.fleet_pick): lo.MinBy over the overrides
+    // in order; score = the spot price of (type, zone) for a spot fleet, else the type's on-demand price
+    const bool spot = r.capacity_type == KP_CT_SPOT;
+    int32_t pick = -1;
+    double best = 0.0;
+    for (int k = 0; k < r.n_types; k++, tp++) {
+        const int32_t t = tys[(size_t)i * M + k];
+        if (type_ids && tp < cap_type_ids) type_ids[tp] = t;
+        // override offerings of slot k: bit j = offering row off_begin[t] + j, ascending
+        for (uint64_t m = ov[(size_t)i * M + k]; m; m &= m - 1, op++) {
+            const int32_t row = c->l_off_begin[t] + __builtin_ctzll(m);
+            if (override_offerings && op < cap_overrides) override_offerings[op] = row;
+            double sc = DBL_MAX;
+            const int nO = (int)c->l_ct.size();
+            for (int f = c->l_off_begin[t]; f < c->l_off_begin[t + 1]; f++) {
+                if (spot ? (c->l_ct[f] == KP_CT_SPOT &&
+                            c->l_off_val[(size_t)KL_ROLE_ZONE * nO + f] == c->l_off_val[(size_t)KL_ROLE_ZONE * nO + row])
+                         : c->l_ct[f] == KP_CT_ON_DEMAND) {
+                    sc = c->l_price[f];
+                    break;
+                }
+            }
+            if (pick < 0 || best == 0.0 || (sc != 0.0 && sc < best)) {
+                pick = row;
+                best = sc;
+            }
+        }
+    }
+    r.fleet_pick = r.status == KP_OK ? pick : -1;
+}
+
 extern "C" kp_status kp_launch_select(kp_ctx* ctx, int32_t n, const kp_launch_request* requests,
                                       int32_t max_instance_types, kp_launch_result* results, int32_t* type_ids,
                                       int32_t cap_type_ids, int32_t* override_offerings, int32_t cap_overrides) try {
@@ -4478,15 +4772,6 @@ extern "C" kp_status kp_launch_select(kp_ctx* ctx, int32_t n, const kp_launch_re
     int64_t* const rq = c->p_l_rq.p;
     memset(rq, 0, (size_t)std::max(1, n) * R * sizeof(int64_t));
     const int roles[KL_ROLES] = {c->key_zone, c->key_ct, c->key_zoneid, c->key_resvid, c->key_resvtype};
-    struct Chunk {
-        std::vector<KlKey> keys;
-        std::vector<KlMinKey> mins;
-        std::vector<uint64_t> words;
-        std::vector<IReq> scratch;
-        std::vector<uint8_t> constrained;
-        kp_status st = KP_OK;
-        std::string msg;
-    };
     for (int x = 0; x < 3; x++) c->ct_vid[x] = c->key_ct >= 0 ? c->cat.keys[c->key_ct].find(kCtNames[x]) : -1;
     int nthr = std::max(1, std::min<int>({16, (int)std::thread::hardware_concurrency(), (n + 255) / 256}));
     if (const char* e = getenv("KPSIM_LAUNCH_THREADS")) nthr = std::max(1, std::min(nthr, atoi(e)));  // diagnostics
@@ -4503,131 +4788,6 @@ extern "C" kp_status kp_launch_select(kp_ctx* ctx, int32_t n, const kp_launch_re
     // catalog keys that are well-known labels (undefined on a request: no constraint), computed once per call
     std::vector<uint8_t> wk(Kc, 0);
     for (int kc = 0; kc < Kc; kc++) wk[kc] = well_known(c->cat.keys[kc].name) ? 1 : 0;
-    auto encode_one = [&](int i, Chunk& ch) -> bool {
-        std::vector<KlKey>& keys = ch.keys;
-        std::vector<KlMinKey>& mins = ch.mins;
-        std::vector<uint64_t>& words = ch.words;
-        auto err = [&](kp_status st, const char* m) {
-            ch.st = st;
-            ch.msg = m;
-            return false;
-        };
-        const kp_launch_request& lr = requests[i];
-        if (lr.n_requirements < 0 || (lr.n_requirements > 0 && !lr.requirements)) return err(KP_E_INVALID, "bad request");
-        // NewNodeSelectorRequirementsWithMinValues: Add = intersect per key, in catalog value-id space (values no type
-        // or offering carries are kept by name only: they decide whether a set is empty)
-        // ch.scratch holds reusable IReq slots: the first nm are this request's merged requirements
-        std::vector<IReq>& slots = ch.scratch;
-        size_t nm = 0;
-        for (int j = 0; j < lr.n_requirements; j++) {
-            const kp_requirement& r = lr.requirements[j];
-            if (!r.key || r.op < 0 || r.op > 5) return err(KP_E_INVALID, "bad requirement");
-            if (nm == slots.size()) slots.emplace_back();
-            IReq& q = slots[nm];
-            ireq_fill(c, r, q);
-            IReq* hit = nullptr;
-            for (size_t x = 0; x < nm; x++)
-                if (slots[x].kc == q.kc && (q.kc >= 0 || !strcmp(slots[x].name, q.name))) hit = &slots[x];
-            if (hit) {
-                ireq_norm(q);
-                ireq_norm(*hit);
-                *hit = ireq_intersection(c, q, *hit);
-            }
-            else nm++;
-        }
-        std::sort(slots.begin(), slots.begin() + nm, [](const IReq& a, const IReq& b) { return strcmp(a.name, b.name) < 0; });
-        struct View {  // the merged requirements of this request
-            const IReq* b;
-            const IReq* e;
-            const IReq* begin() const { return b; }
-            const IReq* end() const { return e; }
-        } m{slots.data(), slots.data() + nm};
-        if (lr.requests)
-            for (int r = 0; r < R; r++) rq[(size_t)i * R + r] = lr.requests[r];
-        KlReq& q = reqs[i];
-        q = KlReq{};
-        q.key_off = (int)keys.size();
-        int woff_of[KL_ROLES];
-        for (int r = 0; r < KL_ROLES; r++) woff_of[r] = -1;
-        const IReq* role_req[KL_ROLES] = {};
-        std::vector<uint8_t>& constrained = ch.constrained;
-        constrained.assign(Kc, 0);
-        for (const IReq& sq : m) {
-            const int kc = sq.kc;
-            if (kc < 0) continue;  // no type or offering carries the key: absent on both sides, never constrains
-            constrained[kc] = 1;
-            const KeyDict& kd = c->cat.keys[kc];
-            const int nv = (int)kd.vals.size();
-            const int woff = (int)words.size();
-            words.resize(words.size() + std::max<size_t>(1, (nv + 63) / 64), 0ull);
-            // bit v ⇔ Has(vals[v]); In sets visit only their own values, complements start full and clear theirs
-            if (!sq.comp) {
-                for (int v : sq.ids) words[woff + v / 64] |= 1ull << (v % 64);
-            } else {
-                const bool bounded = sq.has_gt || sq.has_lt;
-                for (int vv = 0; vv < nv; vv++)
-                    if (!bounded || ireq_within(sq, kd.vals[vv])) words[woff + vv / 64] |= 1ull << (vv % 64);
-                for (int v : sq.ids) words[woff + v / 64] &= ~(1ull << (v % 64));
-            }
-            const int op = sq.op();
-            KlKey kk{kc, c->cat_multi[kc], 0u, woff};
-            kk.flags = (c->cat_kflags[kc] & KF_CAT_MULTI) ? KLK_MULTI : KLK_SINGLE;
-            if (op == 1 || op == 3) kk.flags |= KLK_DNE_OK;
-            if (c->cat_kflags[kc] != 0) keys.push_back(kk);
-            for (int r = 0; r < KL_ROLES; r++)
-                if (roles[r] == kc) {
-                    woff_of[r] = woff;
-                    role_req[r] = &sq;
-                }
-        }
-        q.n_keys = (int)keys.size() - q.key_off;
-        q.und_off = (int)keys.size();
-        for (int kc = 0; kc < Kc; kc++) {
-            if (c->cat_kflags[kc] == 0 || constrained[kc] || wk[kc]) continue;
-            KlKey kk{kc, c->cat_multi[kc], (c->cat_kflags[kc] & KF_CAT_MULTI) ? KLK_MULTI : KLK_SINGLE, 0};
-            keys.push_back(kk);
-        }
-        q.n_und = (int)keys.size() - q.und_off;
-        for (int r = 0; r < KL_ROLES; r++) {
-            const int kc = roles[r];
-            KlRole& ro = q.role[r];
-            ro = KlRole{KLR_PASS, 0u, 0, 0};
-            if (kc < 0) continue;
-            if (woff_of[r] >= 0) {
-                ro.mode = KLR_CONSTRAINED;
-                ro.woff = woff_of[r];
-                const int op = role_req[r]->op();
-                if (op == 1 || op == 3) ro.flags = KLK_DNE_OK;
-            } else if (!wk[kc]) {
-                ro.mode = KLR_FAIL_IN;
-            }
-        }
-        const IReq* ct = nullptr;
-        for (const IReq& x : m)
-            if (c->key_ct >= 0 ? x.kc == c->key_ct : !strcmp(x.name, "karpenter.sh/capacity-type")) ct = &x;
-        for (int x = 0; x < 3; x++) q.ct_has[x] = ct == nullptr ? 1 : (ireq_has(c, *ct, c->ct_vid[x], kCtNames[x]) ? 1 : 0);
-        q.min_off = (int)mins.size();
-        for (const IReq& sq : m) {
-            if (!sq.has_min) continue;
-            q.has_min = 1;
-            const int kc = sq.kc;
-            KlMinKey mk{-1, -1, 0, sq.minv};
-            if (kc >= 0 && c->cat_kflags[kc] != 0) {
-                mk.k = kc;
-                mk.mi = (c->cat_kflags[kc] & KF_CAT_MULTI) ? c->cat_multi[kc] : -1;
-                mk.nvals = (int)c->cat.keys[kc].vals.size();
-                if (mk.nvals > KP_MAX_MIN_WORDS * 64) return err(KP_E_UNSUPPORTED, "minValues key with > 4096 values");
-            } else {
-                mk.k = 0;  // no type carries the key: zero distinct values
-                mk.mi = -1;
-                mk.nvals = 0;
-                if (mk.minv > 0) mk.minv = INT32_MAX;
-            }
-            mins.push_back(mk);
-        }
-        q.n_min = (int)mins.size() - q.min_off;
-        return true;
-    };
     // Pipeline over sub-batches: sub-batch b is encoded on the host threads while the kernel of b-1 runs, and the
     // results of b-1 are expanded once its download has landed.  The request rows (KlReq, requests) and the result
     // rows live at their batch positions; the key / minValues / word tables of sub-batch b go to staging set b & 1,
@@ -4672,7 +4832,6 @@ extern "C" kp_status kp_launch_select(kp_ctx* ctx, int32_t n, const kp_launch_re
     g0.off_avail = c->d_l_avail.p;
     g0.off_rcap = c->d_l_rcap.p;
     const int32_t* const hdr = c->p_l_hdr.p;
-    const int32_t* const tys = c->p_l_types.p;
     const uint64_t* const ov = c->p_l_over.p;
     // result rows: counts first (type_offset / override_offset are prefix sums), then the lists, per thread range
     std::vector<int64_t> toff(n + 1, 0), ooff(n + 1, 0);
@@ -4718,47 +4877,8 @@ extern "C" kp_status kp_launch_select(kp_ctx* ctx, int32_t n, const kp_launch_re
         }
         par(s0, s1, [&](int i0, int i1) {
             for (int i = i0; i < i1; i++) {
-                const int32_t* h = &hdr[(size_t)i * KL_HDR];
-                kp_launch_result& r = results[i];
-                r.status = h[0];
-                r.failed_filter = h[1];
-                r.capacity_type = h[2];
-                r.n_types = h[3];
-                r.n_options = h[5];
-                for (int f = 0; f < KP_N_FILTERS; f++) r.rejected[f] = h[8 + f];
-                r.type_offset = (int32_t)toff[i];
-                r.override_offset = (int32_t)ooff[i];
-                r.n_overrides = (int32_t)(ooff[i + 1] - ooff[i]);
-                int64_t tp = toff[i], op = ooff[i];
-                // kwok CreateFleet's lowest-price pick (kpsim.h kp_launch_result.fleet_pick): lo.MinBy over the overrides
-                // in order; score = the spot price of (type, zone) for a spot fleet, else the type's on-demand price
-                const bool spot = r.capacity_type == KP_CT_SPOT;
-                int32_t pick = -1;
-                double best = 0.0;
-                for (int k = 0; k < r.n_types; k++, tp++) {
-                    const int32_t t = tys[(size_t)i * M + k];
-                    if (type_ids && tp < cap_type_ids) type_ids[tp] = t;
-                    // override offerings of slot k: bit j = offering row off_begin[t] + j, ascending
-                    for (uint64_t m = ov[(size_t)i * M + k]; m; m &= m - 1, op++) {
-                        const int32_t row = c->l_off_begin[t] + __builtin_ctzll(m);
-                        if (override_offerings && op < cap_overrides) override_offerings[op] = row;
-                        double sc = DBL_MAX;
-                        const int nO = (int)c->l_ct.size();
-                        for (int f = c->l_off_begin[t]; f < c->l_off_begin[t + 1]; f++) {
-                            if (spot ? (c->l_ct[f] == KP_CT_SPOT &&
-                                        c->l_off_val[(size_t)KL_ROLE_ZONE * nO + f] == c->l_off_val[(size_t)KL_ROLE_ZONE * nO + row])
-                                     : c->l_ct[f] == KP_CT_ON_DEMAND) {
-                                sc = c->l_price[f];
-                                break;
-                            }
-                        }
-                        if (pick < 0 || best == 0.0 || (sc != 0.0 && sc < best)) {
-                            pick = row;
-                            best = sc;
-                        }
-                    }
-                }
-                r.fleet_pick = r.status == KP_OK ? pick : -1;
+                launch_expand_row(c, i, M, toff[i], ooff[i], ooff[i + 1] - ooff[i], results[i], type_ids, cap_type_ids,
+                                  override_offerings, cap_overrides);
             }
         });
         ms_exp += ms_between(tx, clk::now());
@@ -4778,7 +4898,7 @@ extern "C" kp_status kp_launch_select(kp_ctx* ctx, int32_t n, const kp_launch_re
         if (!c->pool.run(nt, [&](int ti) {
                 const int i0 = s0 + (int)((int64_t)ns * ti / nt), i1 = s0 + (int)((int64_t)ns * (ti + 1) / nt);
                 for (int i = i0; i < i1; i++)
-                    if (!encode_one(i, chunks[ti])) return;
+                    if (!launch_encode_one(c, requests[i], i, chunks[ti], wk, roles)) return;
             }))
             host_err = true;
         if (host_err) {

@@ -346,7 +346,7 @@ __global__ void iota_kernel(int32_t* out, int n) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers (called from kp_host.cpp)
+// launchers (called from kp_host.cpp; prototypes in kp_host.h)
 // ------------------------------------------------------------------------------------------------
 #include <hipcub/hipcub.hpp>
 

@@ -10,9 +10,7 @@
 #include <cstring>
 
 #include "hip/hip_runtime.h"
-#include "../../karpenter-provider-aws_amd/csrc/kp_cons.h"
-#include "../../karpenter-provider-aws_amd/csrc/kp_launch.h"
-#include "../../karpenter-provider-aws_amd/csrc/kp_layout.h"
+#include "../../karpenter-provider-aws_amd/csrc/kp_host.h"  // the launchers' prototypes, shared with kp_host.cpp
 
 static thread_local int t_device = 0;
 static int n_devices() {
@@ -93,7 +91,7 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     return hipSuccess;
 }
 
-// ---- kernel launchers (the real ones live in kp_kernels.hip / kp_consolidate.hip / kp_launch.hip) ----
+// ---- kernel launchers (declared in kp_host.h; the real ones live in kp_kernels.hip / kp_consolidate.hip / kp_launch.hip) ----
 size_t kp_ffd_shared_bytes() { return 0; }
 size_t kp_ffd_shared_bytes_topo() { return 0; }
 bool kp_ffd_plan_lds(KpDev& d, int) {
