@@ -219,6 +219,20 @@ typedef struct kp_existing_node {
     const int64_t* requests;                 /* [R] remaining daemonset requests (initial n.requests) */
 } kp_existing_node;
 
+/*
+ * A host port of a pod: one entry per container port with hostPort != 0 ([core] scheduling/hostportusage.go,
+ * restated in DESIGN.md §4 "Host ports").  Two entries conflict iff protocol and port are equal and either the IPs
+ * are equal or one of them is unspecified; two different specific IPs on one protocol and port do not conflict.
+ * NodeClaim.Add / ExistingNode.Add fail when a port of the pod conflicts with a port the NodeClaim or node already
+ * holds; a successful Add records the pod's ports, a failed one changes nothing.
+ */
+enum { KP_PROTO_TCP = 0, KP_PROTO_UDP = 1, KP_PROTO_SCTP = 2 };
+typedef struct kp_host_port {
+    const char* ip;                          /* hostIP; NULL, "", "0.0.0.0" or "::": unspecified (matches every IP) */
+    int32_t protocol;                        /* KP_PROTO_* (the Kubernetes default is TCP) */
+    int32_t port;                            /* hostPort, != 0 */
+} kp_host_port;
+
 typedef struct kp_solve_input {
     int32_t n_nodepools;
     const kp_nodepool* nodepools;
@@ -234,6 +248,18 @@ typedef struct kp_solve_input {
     int32_t n_bound;
     const int32_t* bound_node;               /* [n_bound] index into existing */
     const int32_t* bound_class;              /* [n_bound] index into classes (labels, namespace, terms) */
+    /* Host ports, as three CSR side tables (offsets + entries); a NULL offsets array means "none", so a
+       zero-initialised input behaves as one without host ports.  The dictionary of distinct (protocol, port, IP)
+       over one input is capped at 256 bits (KP_E_UNSUPPORTED beyond, never approximated). */
+    const int32_t* class_port_offsets;       /* [n_classes+1] or NULL: host ports of every pod of the class */
+    const kp_host_port* class_ports;
+    const int32_t* nodepool_port_offsets;    /* [n_nodepools+1] or NULL: host ports of the NodePool's daemonset pods
+                                                (daemonHostPortUsage): every new NodeClaim of the pool starts with them */
+    const kp_host_port* nodepool_ports;
+    const int32_t* existing_port_offsets;    /* [n_existing+1] or NULL: host ports of all pods bound to the node
+                                                (StateNode.HostPortUsage()); in a kp_consolidate_input this includes the
+                                                reschedulable pods of candidates, as `available` already does */
+    const kp_host_port* existing_ports;
 } kp_solve_input;
 
 /* Per-solve counters: evaluation counts feed the algorithmic-bytes roofline. */
@@ -386,7 +412,10 @@ typedef struct kp_candidate {
 } kp_candidate;
 
 typedef struct kp_consolidate_input {
-    kp_solve_input cluster;          /* nodepools, classes, pods (pending + reschedulable), existing = all state nodes */
+    kp_solve_input cluster;          /* nodepools, classes, pods (pending + reschedulable), existing = all state nodes;
+                                        host-port tables as in a Solve: an existing node's table holds the ports of all
+                                        pods bound to it, the reschedulable pods of candidates included (as `available`
+                                        does); the ports of the pods a probe places are private to that probe */
     const uint8_t* initialized;      /* [n_existing] StateNode.Initialized(); NULL: all initialized */
     int32_t n_pending;               /* provisioner.GetPendingPods, indices into cluster.pods */
     const int32_t* pending;

@@ -115,4 +115,11 @@ struct KpCons {
     int32_t off_hdr, off_words, off_rem, off_excl, off_mod, off_init, off_xtc, off_touch, off_hmod, off_cmax, off_hs, off_hpos;
     int32_t off_mutn, off_rcap;
     int32_t lds_bytes;
+    // host ports (KpDev.PW > 0): a probe that reschedules a port-carrying pod is a MUT probe (mut_s / mut_m), so it runs
+    // serially on the FULL variant's MUT instantiation.  Its dynamic state is private to it: one overlay entry (node,
+    // class mask) per port pod it has put on an existing node, tested against each candidate node of a port pod, and
+    // the port mask of its in-flight NodeClaim (registers).  pov_cap >= the pods of any probe.
+    int32_t pov_cap;
+    int32_t* pov_node;          // [FULL workers][pov_cap]
+    uint64_t* pov_mask;         // [FULL workers][pov_cap][PW]
 };

@@ -335,6 +335,16 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
         // a MUT probe reschedules a mutator's pod: the fast variants hand it over, the MUT variant runs it serially
         const bool mutp = k.mut && __builtin_amdgcn_readfirstlane(single ? k.mut_s[gp] : k.mut_m[gp]) != 0;
         int n_ov = 0;  // MUT: node digest copies taken by this probe
+        // host ports (MUT probes of a pass with d.PW > 0): overlay entries of this probe, and the used ports of its
+        // in-flight NodeClaim (lane w: word w)
+        int n_pov = 0;
+        uint64_t nc_pm = 0;
+        int32_t* const pov_node = (MUT && d.PW > 0) ? k.pov_node + (size_t)wid * k.pov_cap : nullptr;
+        uint64_t* const pov_mask = (MUT && d.PW > 0) ? k.pov_mask + (size_t)wid * k.pov_cap * d.PW : nullptr;
+        // the ports of class c meet mask m (lane w: word w)
+        auto ports_hit = [&](uint64_t m, int c) -> bool {
+            return ballot(lane < d.PW && (m & d.cls_ports[(size_t)c * d.PW + (lane < d.PW ? lane : 0)]) != 0) != 0;
+        };
         for (int i = lane; i < NT * R; i += 64) rem[i] = d.remaining[i];
         if (k.use_cmax)
             for (int i = lane; i < EW * KP_LDS_AXES; i += 64) cmax[i] = k.cmax0[i];
@@ -538,18 +548,43 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
         };
         // MUT: class c's compatible nodes of chunk w (xw from XT) with the nodes this probe changed re-evaluated against
         // their copies: taints tolerated ∧ static fit ∧ Requirements.Compatible(node copy, class)
+        // ... and, for a port-carrying class, without the nodes on which this probe has put a pod whose ports meet the
+        // class's (the overlay; the ports of bound pods are in XT already)
         auto mut_patch = [&](int c, int w, uint64_t xw) -> uint64_t {
             if (!(MUT && mutp)) return xw;
             const uint64_t mw = uni64(mutn[w] & ~excl[w]);
-            if (!mw) return xw;
-            bool ok = false;
-            if ((mw >> lane) & 1ull) {
-                const int j = w * 64 + lane;
-                const int s = ld32(&ov_slot[j]);
-                ok = d.ex_static[j] && ((d.ex_tol[(size_t)c * EW + w] >> lane) & 1ull) &&
-                     node_compatible(d, ov_hdr + (size_t)s * K, ov_words + (size_t)s * d.DW, c);
+            if (mw) {
+                bool ok = false;
+                if ((mw >> lane) & 1ull) {
+                    const int j = w * 64 + lane;
+                    const int s = ld32(&ov_slot[j]);
+                    ok = d.ex_static[j] && ((d.ex_tol[(size_t)c * EW + w] >> lane) & 1ull) &&
+                         node_compatible(d, ov_hdr + (size_t)s * K, ov_words + (size_t)s * d.DW, c);
+                    // the recomputed bit keeps the static host-port conflict existing_mask_kernel folded into XT: a
+                    // port of the class against the ports of the pods bound to the node
+                    for (int pw = 0; pw < d.PW && ok; pw++)
+                        ok = !(d.ex_ports0[(size_t)j * d.PW + pw] & d.cls_ports[(size_t)c * d.PW + pw]);
+                }
+                xw = uni64((xw & ~mw) | ballot(ok));
             }
-            return uni64((xw & ~mw) | ballot(ok));
+            if (d.PW > 0 && n_pov > 0 && (d.cls_flags[c] & CF_PORTS)) {
+                for (int b = 0; b < n_pov; b += 64) {
+                    const int i = b + lane;
+                    int node = -1;
+                    if (i < n_pov) {
+                        node = ld32(&pov_node[i]);
+                        uint64_t x = 0;
+                        if ((node >> 6) == w)
+                            for (int pw = 0; pw < d.PW; pw++)
+                                x |= ld64u(&pov_mask[(size_t)i * d.PW + pw]) & d.cls_ports[(size_t)c * d.PW + pw];
+                        if (!x) node = -1;
+                    }
+                    for (uint64_t m = ballot(node >= 0); m; m &= m - 1)
+                        xw &= ~(1ull << (rl32(node, __ffsll((unsigned long long)m) - 1) & 63));
+                }
+                xw = uni64(xw);
+            }
+            return xw;
         };
         // MUT: ExistingNode.Add's requirement merge of a pod of class c placed on node j (nodeRequirements.Add(pod
         // requirements), then .Add(topology requirements): for a topology class ws holds the merged class keys).  The
@@ -1023,6 +1058,18 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                     topo_record<true>(d, S.CC, S.ws, nh, nwd, jf, -1, false, lane, jf, &P);
                 }
                 if (MUT && mutp) mut_commit(c, jf, TOPO && (cflags & CF_TOPO));
+                // a full overlay slab (prepare sizes it by the pods of the largest probe, so this does not happen) must
+                // not let a later same-port pod join the node: the probe ends NONE, as after any error
+                if (MUT && mutp && d.PW > 0 && (d.cls_flags[c] & CF_PORTS) && n_pov >= k.pov_cap) bad = true;
+                if (MUT && mutp && d.PW > 0 && (d.cls_flags[c] & CF_PORTS) && n_pov < k.pov_cap) {
+                    // the node holds the pod's ports for the rest of this probe
+                    if (lane == 0) __hip_atomic_store(&pov_node[n_pov], jf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (lane < d.PW)
+                        __hip_atomic_store(&pov_mask[(size_t)n_pov * d.PW + lane], d.cls_ports[(size_t)c * d.PW + lane],
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    n_pov++;
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
                 st_placed++;
                 if (!pend) {
                     if ((cinit >> (jf & 63)) & 1ull) ok_np++;
@@ -1038,7 +1085,9 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
             bool placed = false;
             const long long cn0 = prof ? __builtin_amdgcn_s_memtime() : 0;
             const int64_t* preq = d.pod_req + (size_t)p * R;
-            if (n_nc == 1) {  // NodeClaim.Add on the in-flight NodeClaim
+            // host ports: the pod's ports against the in-flight NodeClaim's (before every shortcut of its Add)
+            const bool cport = MUT && mutp && d.PW > 0 && (d.cls_flags[c] & CF_PORTS);
+            if (n_nc == 1 && !(cport && ports_hit(nc_pm, c))) {  // NodeClaim.Add on the in-flight NodeClaim
                 if (S.CC.cls != c) fill_class_cache<TOPO>(d, c, S.CC, lane, 64, TOPO ? S.born : 0ull);
                 EvalIn a;
                 a.Ahdr = nch;
@@ -1087,12 +1136,15 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                     if (TOPO && (cflags & CF_TOPO)) topo_record<true>(d, S.CC, S.ws, nch, ncw, E, nc_tmpl, true, lane, -1, &P);
                     placed = true;
                 }
+                if (cport && placed && lane < d.PW) nc_pm |= d.cls_ports[(size_t)c * d.PW + lane];
             }
             if (!placed) {  // new NodeClaim from the templates in weight order
                 for (int j = 0; j < NT; j++) {
                     uint64_t o = (lane < TW && d.tmpl_ok[j]) ? d.tmpl_opts[(size_t)j * TW + lane] : 0;
                     o = limit_filter_rem(d, j, o, rem, lane);
                     if (!ballot(o != 0)) continue;
+                    // the template's daemonset holds a port of the pod: NewNodeClaim's Add fails
+                    if (cport && ports_hit(lane < d.PW ? d.tmpl_ports[(size_t)j * d.PW + lane] : 0ull, c)) continue;
                     if (S.CC.cls != c) fill_class_cache<TOPO>(d, c, S.CC, lane, 64, TOPO ? S.born : 0ull);
                     EvalIn a;
                     a.Ahdr = d.cls_hdr + (size_t)(d.C + j) * K;
@@ -1139,6 +1191,9 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                         mx = wave_max64(mx);
                         if (lane == 0) rem[j * R + r] -= mx;
                     }
+                    if (MUT && mutp && d.PW > 0)
+                        nc_pm = lane < d.PW ? (d.tmpl_ports[(size_t)j * d.PW + lane] |
+                                               (cport ? d.cls_ports[(size_t)c * d.PW + lane] : 0ull)) : 0ull;
                     nc_tmpl = j;
                     n_nc = 1;
                     nc_lc = c;

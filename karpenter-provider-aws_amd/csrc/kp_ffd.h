@@ -22,6 +22,47 @@ namespace KP_WNS {
 #define KP_TOPO_ON 1
 #endif
 
+// ------------------------------------------------------------------------------------------------
+// Host ports (the PORTS instantiations; DESIGN.md §4 "Host ports")
+// ------------------------------------------------------------------------------------------------
+// The used-port mask at m (a NodeClaim's or an existing node's, written by other waves: agent-scope loads) meets the
+// ports of class c: NodeClaim.Add / ExistingNode.Add of a pod of c fails there.
+__device__ __forceinline__ bool ports_meet(const KpDev& d, const uint64_t* m, int c) {
+    uint64_t x = 0;
+    for (int w = 0; w < d.PW; w++)
+        x |= __hip_atomic_load(const_cast<uint64_t*>(m) + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
+             d.cls_ports[(size_t)c * d.PW + w];
+    return x != 0;
+}
+// One wave: every class whose ports meet the used ports of existing node j loses the node in its compatibility column
+// (XT), so the existing-node scans of the following pops skip it without a test of their own.  Run after whatever
+// recomputes node j's column from its requirements (existing_merge, existing_topo_commit), which knows no ports.
+__device__ inline void existing_ports_mask(const KpDev& d, int j, int lane) {
+    const uint64_t bm = 1ull << (j & 63);
+    for (int cc = lane; cc < d.C; cc += 64)
+        if (ports_meet(d, d.ex_ports + (size_t)j * d.PW, cc))
+            atomicAnd((unsigned long long*)&d.XT[(size_t)cc * d.EW + (j >> 6)], (unsigned long long)~bm);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+// One wave: a pod of port-carrying class c was added to existing node j: the node's used ports gain the class's (c
+// itself then conflicts with the node).
+__device__ inline void existing_ports_commit(const KpDev& d, int j, int c, int lane) {
+    if (lane < d.PW)
+        atomicOr((unsigned long long*)&d.ex_ports[(size_t)j * d.PW + lane], (unsigned long long)d.cls_ports[(size_t)c * d.PW + lane]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    existing_ports_mask(d, j, lane);
+}
+// One wave: NodeClaim nc takes a pod of class c (fresh: it was just created from template tmpl and starts with the
+// template's daemonset ports).
+__device__ __forceinline__ void nodeclaim_ports_commit(const KpDev& d, int nc, int c, bool fresh, int tmpl, int lane) {
+    if (lane < d.PW) {
+        uint64_t* p = d.nc_ports + (size_t)nc * d.PW + lane;
+        const uint64_t base = fresh ? d.tmpl_ports[(size_t)tmpl * d.PW + lane]
+                                    : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(p, base | d.cls_ports[(size_t)c * d.PW + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // ExistingNode.Add's requirement merge of class c into node j (wave 0; only solves whose classes carry
 // NotIn/DoesNotExist keys).  When node j's requirements change, its XT column is recomputed for every class.
 __device__ inline void existing_merge(const KpDev& d, int j, int c, int lane) {
@@ -361,10 +402,19 @@ __device__ inline void topo_record_quick(const KpDev& d, FfdShared& S, int c, in
 // template's taints the pod's class tolerates (NodeClaim.Add's first test; tol bit j = template j) and that passes the
 // topology prefilter of the current pod
 // TOPO: the solve has topology groups (otherwise no pod carries a prefilter and its tests compile out)
-template <bool TOPO>
-__device__ inline void collect_candidates(const KpDev& d, FfdShared& S, const uint32_t* key, const uint16_t* ord,
-                                          const uint8_t* stmpl, uint64_t tol, int N, int start, int buf, int lane) {
+// PORTS: pc >= 0 is the pod's port-carrying class.  A NodeClaim whose used ports meet the class's never becomes a
+// candidate, so it costs no evaluation; the conflict lasts for the whole Solve, so the position also enters the shape's
+// rejection memo (the return value: some position was marked, the caller raises any_rej) and later scans of the shape
+// skip it in the slice window.  Only wave 0 collects, and it writes the memo either inside its fast loop or while the
+// other waves are parked at the round's barrier, so no other wave reads the slice keys meanwhile (the PORTS variant
+// therefore takes the keys as a mutable pointer).
+template <bool TOPO, bool PORTS = false>
+__device__ inline bool collect_candidates(const KpDev& d, FfdShared& S,
+                                          std::conditional_t<PORTS, uint32_t*, const uint32_t*> key, const uint16_t* ord,
+                                          const uint8_t* stmpl, uint64_t tol, int N, int start, int buf, int lane,
+                                          int pc = -1) {
     int cnt = 0, pos = start, next = N;
+    bool marked = false;
     const int tp_n = TOPO ? S.tp_n : 0;  // read once: the stores to cand_pos below would make every use a new LDS read
     // topology pods: at most d.topo_cands candidates per round (the first prefilter survivor usually accepts; fewer waves
     // evaluating leaves each its own SIMD)
@@ -373,6 +423,13 @@ __device__ inline void collect_candidates(const KpDev& d, FfdShared& S, const ui
         const int p = pos + lane;
         bool c = p < N && !(key[p] >> 31);
         if (c) c = (tol >> stmpl[ord[p]]) & 1ull;
+        if (PORTS && pc >= 0) {
+            const bool meet = c && ports_meet(d, d.nc_ports + (size_t)ord[p] * d.PW, pc);
+            if constexpr (PORTS)
+                if (meet) key[p] |= 0x80000000u;
+            marked |= ballot(meet) != 0;
+            c = c && !meet;
+        }
         if (tp_n && c) c = topo_prefilter_pass(d, S, ord[p]);
         const uint64_t m0 = __ballot(c);
         if (tp_n && m0 && cnt + __popcll(m0) < L) {
@@ -387,7 +444,7 @@ __device__ inline void collect_candidates(const KpDev& d, FfdShared& S, const ui
                 S.scan_next[buf] = pos < N ? pos : N;
                 S.scan_done[buf] = pos >= N;
             }
-            return;
+            return marked;
         }
         const uint64_t m = __ballot(c);
         const int rank = cnt + __popcll(m & ((1ull << lane) - 1ull));
@@ -407,6 +464,7 @@ __device__ inline void collect_candidates(const KpDev& d, FfdShared& S, const ui
         S.scan_next[buf] = cnt == L ? next : N;
         S.scan_done[buf] = (cnt < L) || next >= N;
     }
+    return marked;
 }
 
 // types whose Capacity exceeds a NodePool's remaining limits (filterByRemainingResources)
@@ -594,7 +652,11 @@ __device__ inline void block_sort_move(FfdShared& S, SortSlice sl, int tid, int 
 // PROF: the diagnostic twin of an entry point (kp_ffd_prof_*.hip; launched when KPSIM_PROFILE or KPSIM_TRACE_POD is
 // set): stage stamps (s_memtime), the cyc_* / n_* / why counters and the trace records.  The production instantiations
 // compile all of it out: those statistics read 0 there, every other one is exact in both.
-template <bool RESV, bool TOPO, bool PREF, bool HBM = false, bool PROF = false>
+// PORTS: the solve carries host ports.  A pod of a port-carrying class (CF_PORTS) conflicts with its own class, so it is
+// never quick-accepted or batched: it goes to the block, whose candidate collection leaves out the NodeClaims whose used
+// ports meet the class's; the commits maintain the used-port masks (nc_ports, ex_ports) and the existing nodes' columns.
+// Port-free classes of such a solve take the paths they take anywhere.  PORTS = false compiles all of it out.
+template <bool RESV, bool TOPO, bool PREF, bool HBM = false, bool PROF = false, bool PORTS = false>
 __device__ __forceinline__ void ffd_solve(KpDev d) {
     constexpr bool TOPO_ON = KP_TOPO_ON && TOPO;  // the solve has topology groups
     const bool prof = PROF && d.profile;
@@ -810,6 +872,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             int c = S.cur_cls;
             // the current shape's class carries topology (CF_TOPO): such pods are handled by the block
             bool ctopo = TOPO_ON && c >= 0 && (d.cls_flags[c] & CF_TOPO);
+            bool cport = PORTS && c >= 0 && (d.cls_flags[c] & CF_PORTS);  // ... carries host ports
             uint64_t tl = S.cur_tol;
             int pq[KP_LDS_AXES];
 #pragma unroll
@@ -943,6 +1006,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     }
                     c = rl32(vc, off);
                     ctopo = TOPO_ON && (d.cls_flags[c] & CF_TOPO) != 0;
+                    cport = PORTS && (d.cls_flags[c] & CF_PORTS) != 0;
                     tl = rl64(vtol, off);
 #pragma unroll
                     for (int ai = 0; ai < KP_LDS_AXES; ai++) pq[ai] = rl32(vq[ai], off);
@@ -989,6 +1053,11 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         if (d.ex_mayfix) {
                             ex_flush();
                             existing_merge(d, jf, c, lane);
+                            if (PORTS && !cport) existing_ports_mask(d, jf, lane);  // the recomputed column knows no ports
+                        }
+                        if (PORTS && cport) {  // the node holds the class's ports from here on
+                            ex_flush();
+                            existing_ports_commit(d, jf, c, lane);
                         }
                         if (lane == 0) {
                             d.pod_result[p] = -2 - jf;
@@ -1133,7 +1202,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 }
                 const long long t_d = prof_clock(prof);
                 cqscan += t_d - t_c;
-                if (f < N) {
+                if (f < N && !(PORTS && cport)) {  // a port-carrying pod is never quick-accepted: the block takes it
                     const int fl = f - wb;
                     bool wfit = A > 0;  // no witness table (A == 0): every pod is evaluated
 #pragma unroll
@@ -1307,7 +1376,8 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     S.cls_fill = S.CC.cls != c;  // decided before the barrier: fill_class_cache rewrites CC.cls
                     S.topo_pod = 0;
                 }
-                collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, ~0ull, N, f, 0, lane);
+                if (collect_candidates<TOPO_ON, PORTS>(d, S, skey, sord, stmpl, ~0ull, N, f, 0, lane, (PORTS && cport) ? c : -1))
+                    any_rej = 1;
                 break;
             }
             win_flush();
@@ -1387,6 +1457,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             __syncthreads();
             if (wave == 0) {
                 const int placed = existing_topo_scan(d.self, S, pod, lane);
+                if (PORTS && placed >= 0) {  // the column the commit recomputed knows no ports; a port pod adds its own
+                    if (S.CC.flags & CF_PORTS) existing_ports_commit(d, placed, S.cur_cls, lane);
+                    else existing_ports_mask(d, placed, lane);
+                }
                 if (lane == 0) {
                     S.ex_placed = placed;
                     S.cls_fill = 0;
@@ -1448,7 +1522,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                                   : !(slast[nc] == (uint16_t)c || ((cfl & CF_NOKEYS) && ((d.tol[c] >> stmpl[nc]) & 1ull))) ? 3 : 4;
                     S.st[ST_TQ_WHY + why]++;
                 }
-                if (f < N && (cfl & CF_TOPO_QREC) && A > 0 && S.tp_all) {
+                if (f < N && (cfl & CF_TOPO_QREC) && A > 0 && S.tp_all && !(PORTS && (cfl & CF_PORTS))) {
                     const int nc = sord[f], tm = stmpl[nc];
                     const bool absd = slast[nc] == (uint16_t)c || ((cfl & CF_NOKEYS) && ((d.tol[c] >> tm) & 1ull));
                     bool ok = nc < NQ;
@@ -1478,7 +1552,9 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     }
                 }
-                if (!quick) collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, ctol, N, f, 0, lane);
+                if (!quick && collect_candidates<TOPO_ON, PORTS>(d, S, skey, sord, stmpl, ctol, N, f, 0, lane,
+                                                                 (PORTS && (cfl & CF_PORTS)) ? c : -1) && lane == 0)
+                    S.any_rej = 1;
                 if (lane == 0) {
                     S.topo_quick = quick;
                     if (quick) {  // nothing reads these before the next slow-path entry (behind wave 0's fast loop)
@@ -1570,8 +1646,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 }
             }
             if (win >= 0 || S.scan_done[b]) break;
-            if (wave == 0)
-                collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b], b ^ 1, lane);
+            if (wave == 0 &&
+                collect_candidates<TOPO_ON, PORTS>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b],
+                                                   b ^ 1, lane, (PORTS && (S.CC.flags & CF_PORTS)) ? S.cur_cls : -1) && lane == 0)
+                S.any_rej = 1;
             __syncthreads();
             round++;
         }
@@ -1682,8 +1760,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 }
             if (tid == 0) S.st[ST_NC_EVALS] += nc_ > f0 ? nc_ - f0 : 0;
             if (win >= 0 || S.scan_done[b]) break;
-            if (wave == 0)
-                collect_candidates<TOPO_ON>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b], b ^ 1, lane);
+            if (wave == 0 &&
+                collect_candidates<TOPO_ON, PORTS>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b],
+                                                   b ^ 1, lane, (PORTS && (S.CC.flags & CF_PORTS)) ? S.cur_cls : -1) && lane == 0)
+                S.any_rej = 1;
             __syncthreads();
             round++;
         }
@@ -1714,6 +1794,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     topo_record(d, S.CC, S.ws[cw], d.nc_hdr + (size_t)nc * K, d.nc_words + (size_t)nc * d.DW,
                                 d.E + nc, d.nc_tmpl[nc], true, lane, -1, nullptr, S.born);
                 if (lane < TW) d.nc_opts[(size_t)nc * TW + lane] = S.ws[cw].opts[lane];
+                if (PORTS && (S.CC.flags & CF_PORTS)) nodeclaim_ports_commit(d, nc, S.cur_cls, false, 0, lane);
                 if (lane < R && S.pod_req[lane])
                     atomicAdd((unsigned long long*)&d.nc_req[(size_t)nc * R + lane], (unsigned long long)S.pod_req[lane]);
                 if (lane < A && nc < NQ) shr[lane * NQ + nc] = S.ws[cw].hr[lane];
@@ -1764,6 +1845,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                                 d.cls_words + (size_t)(d.C + jj) * d.DW, d.E + n, jj, true, lane, -1, nullptr,
                                 S.born);
                 if (lane < TW) d.nc_opts[(size_t)n * TW + lane] = S.ws[cw].opts[lane];
+                if (PORTS) nodeclaim_ports_commit(d, n, S.cur_cls, true, jj, lane);
                 for (int r = lane; r < R; r += 64)
                     __hip_atomic_store(&d.nc_req[(size_t)n * R + r], d.daemon[(size_t)jj * R + r] + S.pod_req[r],
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1806,6 +1888,8 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 for (int j = 0; j < d.NT; j++) {
                     uint64_t o = (lane < TW && d.tmpl_ok[j]) ? d.tmpl_opts[(size_t)j * TW + lane] : 0;
                     o = limit_filter(d, j, o, lane);
+                    // the template's daemonset holds a port of the pod: NewNodeClaim's Add fails
+                    if (PORTS && (S.CC.flags & CF_PORTS) && ports_meet(d, d.tmpl_ports + (size_t)j * d.PW, S.cur_cls)) o = 0;
                     if (!ballot(o != 0)) continue;  // the same for every wave
                     EvalIn a;
                     a.Ahdr = d.cls_hdr + (size_t)(d.C + j) * K;
@@ -1851,6 +1935,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 if (j < d.NT) {
                     uint64_t o = (lane < TW && d.tmpl_ok[j]) ? d.tmpl_opts[(size_t)j * TW + lane] : 0;
                     o = limit_filter(d, j, o, lane);
+                    if (PORTS && (S.CC.flags & CF_PORTS) && ports_meet(d, d.tmpl_ports + (size_t)j * d.PW, S.cur_cls)) o = 0;
                     bool ok = false;
                     if (ballot(o != 0)) {
                         EvalIn a;
@@ -1913,6 +1998,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                                         d.cls_words + (size_t)(d.C + jj) * d.DW, d.E + n, jj, true, lane, -1, nullptr,
                                         S.born);
                         if (lane < TW) d.nc_opts[(size_t)n * TW + lane] = S.ws[wave].opts[lane];
+                        if (PORTS) nodeclaim_ports_commit(d, n, S.cur_cls, true, jj, lane);
                         for (int r = lane; r < R; r += 64)
                             __hip_atomic_store(&d.nc_req[(size_t)n * R + r], d.daemon[(size_t)jj * R + r] + S.pod_req[r],
                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2032,10 +2118,17 @@ using namespace KP_WNS;
 
 // A Solve kernel entry point: ffd_solve<RESV, TOPO, PREF, HBM> under its own name, so kernel traces tell the
 // instantiations apart.  A unit compiled with KP_FFD_PROF (kp_ffd_prof_*.hip) defines the diagnostic twin name_prof.
+// KP_FFD_ENTRY_PORTS: a host-port entry point ffd_solve<RESV, TOPO, PREF = true, HBM, PROF, PORTS = true>.  The PREF code is
+// exact for solves that do not need it (every use is guarded by relax_next / last_ep / best_effort), so the host-port
+// solves share the PREF instantiations instead of doubling their number.
 #ifdef KP_FFD_PROF
 #define KP_FFD_ENTRY(name, ...) \
     __global__ __launch_bounds__(KP_NWAVES * 64) void name##_prof(KpDev d) { ffd_solve<__VA_ARGS__, true>(d); }
+#define KP_FFD_ENTRY_PORTS(name, resv, topo, hbm) \
+    __global__ __launch_bounds__(KP_NWAVES * 64) void name##_prof(KpDev d) { ffd_solve<resv, topo, true, hbm, true, true>(d); }
 #else
 #define KP_FFD_ENTRY(name, ...) \
     __global__ __launch_bounds__(KP_NWAVES * 64) void name(KpDev d) { ffd_solve<__VA_ARGS__, false>(d); }
+#define KP_FFD_ENTRY_PORTS(name, resv, topo, hbm) \
+    __global__ __launch_bounds__(KP_NWAVES * 64) void name(KpDev d) { ffd_solve<resv, topo, true, hbm, false, true>(d); }
 #endif

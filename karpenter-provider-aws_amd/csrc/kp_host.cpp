@@ -5,6 +5,8 @@
 // with KP_E_DEVICE).
 #include <hip/hip_runtime.h>
 
+#include <arpa/inet.h>
+
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -408,6 +410,7 @@ struct kp_ctx {
     std::vector<int64_t> h_remaining;        // NodePool limits at solve start (re-applied by every execute)
     DBuf<uint32_t> d_kflags, d_cls_flags;
     DBuf<uint64_t> d_tol;
+    DBuf<uint64_t> d_cls_ports, d_tmpl_ports, d_ex_ports0, d_ex_ports, d_nc_ports;  // host ports (solve_host_ports)
     DBuf<ReqHdr> d_ex_hdr0, d_ex_hdr;
     DBuf<uint64_t> d_ex_words0, d_ex_words, d_ex_tol, d_XT;
     DBuf<int64_t> d_ex_avail, d_ex_req, d_ex_head;
@@ -430,8 +433,10 @@ struct kp_ctx {
     bool any_min_values = false;             // some template requirement carries minValues
     int max_min_values = 0;                  // the largest minValues among the template requirements
     bool min_multi = false;                  // ... on a multi-valued catalog key (zone, capacity type, ...)
-    std::vector<uint8_t> cons_mutcls;        // per (expanded) class: its NotIn/DoesNotExist merge can change a node's
-                                             // requirements in a way a later decision sees (MUT probes)
+    std::vector<uint8_t> cons_mutcls;        // per (expanded) class: a probe that reschedules its pod carries per-probe
+                                             // node state (MUT probes): its NotIn/DoesNotExist merge can change a node's
+                                             // requirements in a way a later decision sees, or it carries host ports
+                                             // (solve_host_ports: the node then holds them for the rest of the probe)
     // consolidation probes
     DBuf<int32_t> d_retry, d_rank, d_cand_i, d_cand_off, d_cand_pods, d_pending, d_ring, d_ring_last, d_next, d_pnode;
     DBuf<double> d_cand_price;
@@ -455,7 +460,8 @@ struct kp_ctx {
     DBuf<uint64_t> d_rec_words;
     // MUT probes: per-probe flags (single-node by candidate, multi-node by prefix) and the per-worker node requirement
     // copies of the MUT variant
-    DBuf<int32_t> d_mut_s, d_mut_m, d_ov_slot;
+    DBuf<int32_t> d_mut_s, d_mut_m, d_ov_slot, d_pov_node;
+    DBuf<uint64_t> d_pov_mask;
     DBuf<ReqHdr> d_ov_hdr;
     DBuf<uint64_t> d_ov_words;
     int cons_n_mut = 0;                      // probes of the prepared pass that run on the MUT variant
@@ -1998,6 +2004,9 @@ struct SolveEnc {
     std::vector<uint8_t> limit_set;
     std::vector<ReqHdr> exhdr;
     std::vector<int32_t> shape_next;
+    // host ports (solve_host_ports): PW mask words over the solve's port-bit dictionary (0: no host ports anywhere)
+    int PW = 0, port_bits = 0;
+    std::vector<uint64_t> cports, tports, xports;  // [C][PW] classes, [NT][PW] templates' daemonsets, [E][PW] bound pods
 };
 
 static kp_status solve_expand(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
@@ -2379,6 +2388,113 @@ static kp_status solve_existing_digests(kp_ctx* ctx, const kp_solve_input* in, S
     return KP_OK;
 }
 
+// Host ports ([core] scheduling/hostportusage.go, recalled; DESIGN.md §4 "Host ports").  One port-bit dictionary per
+// solve: entries are grouped by (protocol, port); a group gets one wildcard bit plus one bit per distinct specific IP
+// seen anywhere in the input.  An entry with a specific IP owns that IP's bit, an entry with an unspecified IP every
+// bit of its group, so two entries conflict exactly when their bit sets meet, and one mask per class serves both the
+// test against and the commit into a NodeClaim's or node's used-port mask.
+struct HostPortEnt {
+    int32_t proto, port;
+    bool unspec;
+    std::array<uint8_t, 16> ip;
+};
+static bool parse_host_ip(const char* s, HostPortEnt& e) {
+    e.ip.fill(0);
+    e.unspec = true;
+    if (!s || !*s) return true;
+    uint8_t v4[4];
+    if (inet_pton(AF_INET, s, v4) == 1) {  // as Go's net.IP: the IPv4-mapped form, equal to the same address written as IPv6
+        e.ip[10] = e.ip[11] = 0xFF;
+        memcpy(&e.ip[12], v4, 4);
+        e.unspec = (v4[0] | v4[1] | v4[2] | v4[3]) == 0;
+        return true;
+    }
+    if (inet_pton(AF_INET6, s, e.ip.data()) != 1) return false;
+    bool zero = true;
+    for (int i = 0; i < 16; i++) zero &= e.ip[i] == 0;
+    bool v4zero = e.ip[10] == 0xFF && e.ip[11] == 0xFF;
+    for (int i = 0; i < 16; i++)
+        if (i != 10 && i != 11) v4zero &= e.ip[i] == 0;
+    e.unspec = zero || v4zero;
+    return true;
+}
+static kp_status solve_host_ports(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int C = in->n_classes, NT = se.NT, E = se.E;
+    const int C0 = ctx->pref.n_input;  // the tables are indexed by input class
+    std::string err;
+    auto rows = [&](const int32_t* off, const kp_host_port* ent, int n, std::vector<std::vector<HostPortEnt>>& out) -> bool {
+        out.assign(n, {});
+        if (!off) return true;
+        if (off[0] != 0 || (off[n] > 0 && !ent)) return err = "host-port table offsets", false;
+        for (int i = 0; i < n; i++) {
+            if (off[i + 1] < off[i]) return err = "host-port table offsets", false;
+            for (int q = off[i]; q < off[i + 1]; q++) {
+                HostPortEnt e;
+                e.proto = ent[q].protocol;
+                e.port = ent[q].port;
+                if (e.proto < KP_PROTO_TCP || e.proto > KP_PROTO_SCTP) return err = "host port: unknown protocol", false;
+                if (e.port < 1 || e.port > 65535) return err = "host port out of 1..65535", false;
+                if (!parse_host_ip(ent[q].ip, e)) return err = std::string("host port: bad IP ") + ent[q].ip, false;
+                out[i].push_back(e);
+            }
+        }
+        return true;
+    };
+    std::vector<std::vector<HostPortEnt>> rc, rt, rx;
+    if (!rows(in->class_port_offsets, in->class_ports, C0, rc) || !rows(in->nodepool_port_offsets, in->nodepool_ports, in->n_nodepools, rt) ||
+        !rows(in->existing_port_offsets, in->existing_ports, E, rx))
+        return fail(ctx, KP_E_INVALID, err);
+    // the dictionary: per (protocol, port) group, its specific IPs in address order
+    std::map<std::pair<int32_t, int32_t>, std::map<std::array<uint8_t, 16>, int>> groups;
+    for (auto* tab : {&rc, &rt, &rx})
+        for (auto& r : *tab)
+            for (auto& e : r) {
+                auto& g = groups[{e.proto, e.port}];
+                if (!e.unspec) g[e.ip] = 0;
+            }
+    std::map<std::pair<int32_t, int32_t>, int> gbase;  // the group's wildcard bit; its IPs follow
+    int nbits = 0;
+    for (auto& g : groups) {
+        gbase[g.first] = nbits++;
+        for (auto& ip : g.second) ip.second = nbits++;
+    }
+    se.port_bits = nbits;
+    if (nbits > KP_MAX_PORT_WORDS * 64)
+        return fail(ctx, KP_E_UNSUPPORTED, "host ports: the input's port dictionary needs " + std::to_string(nbits) +
+                                           " bits (one per (protocol, port) plus one per specific IP of it); at most " +
+                                           std::to_string(KP_MAX_PORT_WORDS * 64) + " are supported");
+    const int PW = se.PW = (nbits + 63) / 64;
+    if (PW == 0) return KP_OK;
+    auto mask = [&](const std::vector<HostPortEnt>& r, uint64_t* m) {
+        for (auto& e : r) {
+            const auto& g = groups[{e.proto, e.port}];
+            const int b0 = gbase[{e.proto, e.port}];
+            if (e.unspec) {
+                for (int b = b0; b <= b0 + (int)g.size(); b++) m[b / 64] |= 1ull << (b % 64);
+            } else {
+                const int b = g.at(e.ip);
+                m[b / 64] |= 1ull << (b % 64);
+            }
+        }
+    };
+    se.cports.assign((size_t)std::max(C, 1) * PW, 0);
+    se.tports.assign((size_t)std::max(NT, 1) * PW, 0);
+    se.xports.assign((size_t)std::max(E, 1) * PW, 0);
+    for (int i = 0; i < C; i++) {  // every relaxation stage of an input class carries the class's ports
+        const int o = ctx->pref.origin.empty() ? i : ctx->pref.origin[i];
+        mask(rc[o], &se.cports[(size_t)i * PW]);
+        bool any = false;
+        for (int w = 0; w < PW; w++) any |= se.cports[(size_t)i * PW + w] != 0;
+        if (any) se.cflags[i] |= CF_PORTS;
+        // consolidation: a probe that reschedules a port-carrying pod keeps private port state (KpCons::pov_node) and
+        // runs where the probes of mutators run
+        if (any && i < (int)ctx->cons_mutcls.size()) ctx->cons_mutcls[i] = 1;
+    }
+    for (int j = 0; j < NT; j++) mask(rt[se.npo[j]], &se.tports[(size_t)j * PW]);
+    for (int j = 0; j < E; j++) mask(rx[j], &se.xports[(size_t)j * PW]);
+    return KP_OK;
+}
+
 static kp_status solve_pods(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
     const int R = ctx->R, P = in->pods.n_pods, C = in->n_classes, NT = se.NT;
     // ---- pods ----
@@ -2594,6 +2710,12 @@ static kp_status solve_upload(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& s
     HIPCHK(c->d_tmpl_opts.ensure((size_t)std::max(NT, 1) * TW));
     HIPCHK(c->d_tmpl_ok.ensure(std::max(NT, 1)));
     HIPCHK(c->d_tol.upload(se.tol, s));
+    if (se.PW > 0) {
+        HIPCHK(c->d_cls_ports.upload(se.cports, s));
+        HIPCHK(c->d_tmpl_ports.upload(se.tports, s));
+        HIPCHK(c->d_ex_ports0.upload(se.xports, s));
+        HIPCHK(c->d_ex_ports.ensure(se.xports.size()));
+    }
     HIPCHK(c->d_daemon.upload(se.daemon, s));
     HIPCHK(c->d_limit_set.upload(se.limit_set, s));
     HIPCHK(c->d_remaining.upload(se.remaining, s));
@@ -2650,6 +2772,15 @@ static kp_status solve_plan_nodeclaims(kp_ctx* ctx, const kp_solve_input* in, So
                 else if (g.type == KP_TOPO_SPREAD && g.skew > 0) n = (m + g.skew - 1) / g.skew;
                 dense = std::max(dense, n - E);
             }
+        // host ports: the pods that share one port bit take a NodeClaim or node each
+        if (se.PW > 0) {
+            std::vector<int64_t> bcount((size_t)se.PW * 64, 0);
+            for (int o = 0; o < C; o++)
+                for (int w = 0; w < se.PW && ccount[o]; w++)
+                    for (uint64_t m = se.cports[(size_t)o * se.PW + w]; m; m &= m - 1)
+                        bcount[(size_t)w * 64 + __builtin_ctzll(m)] += ccount[o];
+            for (int64_t n : bcount) dense = std::max(dense, n - E);
+        }
     }
     int64_t plan = c->nc_cap_once > 0 ? c->nc_cap_once : KP_NC_FIRST;
     c->nc_cap_once = 0;
@@ -2663,6 +2794,7 @@ static kp_status solve_plan_nodeclaims(kp_ctx* ctx, const kp_solve_input* in, So
     HIPCHK(c->d_nc_tmpl.ensure(NCcap));
     HIPCHK(c->d_nc_held.ensure((size_t)NCcap * std::max(1, c->h_ro.ridw)));
     HIPCHK(c->d_nc_rlive.ensure(NCcap));
+    if (se.PW > 0) HIPCHK(c->d_nc_ports.ensure((size_t)NCcap * se.PW));
     HIPCHK(c->d_qbuf.ensure(std::max(P, 1)));
     HIPCHK(c->d_last_len.ensure(std::max(P, 1)));
     HIPCHK(c->d_pod_result.ensure(std::max(P, 1)));
@@ -3060,6 +3192,10 @@ static kp_status solve_fill_dev(kp_ctx* ctx, const kp_solve_input* in, SolveEnc&
     d.NT = NT;
     DEV(cls_koff); DEV(cls_keys); DEV(cls_wsoff); DEV(cls_hdr); DEV(cls_words); DEV(cls_flags); DEV(V); DEV(tmpl_rows);
     DEV(tmpl_opts); DEV(tmpl_ok); DEV(tol); DEV(daemon); DEV(limit_set); DEV(remaining);
+    d.PW = se.PW;  // host ports
+    if (se.PW > 0) {
+        DEV(cls_ports); DEV(tmpl_ports); DEV(ex_ports0); DEV(ex_ports); DEV(nc_ports);
+    }
     HIPCHK(c->d_tmpl_lmask.ensure((size_t)std::max(1, d.NT) * std::max(1, d.TW)));
     DEV(tmpl_lmask); DEV(min_keys);
     d.E = E;
@@ -3195,6 +3331,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     STAGE(solve_digests);
     STAGE(solve_template_tables);
     STAGE(solve_existing_digests);
+    STAGE(solve_host_ports);
     PREP_MARK(2);
     STAGE(solve_pods);  // PREP_MARK(3) sits inside, between the pod passes and shape_next.  Resets ctx->dev and sets its
                         // active axes; solve_topology_tables adds snap_rows, born0 and HN; solve_fill_dev the rest
@@ -3584,7 +3721,8 @@ static kp_status cons_topology_decrements(kp_ctx* ctx, const kp_consolidate_inpu
 }
 
 // mutators (kp_solve_prepare): a probe that reschedules a pod whose class, or a relaxation stage of it, may change a
-// node's requirements runs on the MUT variant (per-probe node requirement copies); the others are unaffected
+// node's requirements, or carries host ports, runs on the MUT variant (per-probe node requirement copies and host-port
+// overlay; CS_MUT counts both kinds); the others are unaffected
 static kp_status cons_mutators(kp_ctx* ctx, const kp_consolidate_input* in) {
     const int NC = in->n_candidates;
     hipStream_t s = ctx->stream;
@@ -3895,6 +4033,13 @@ static kp_status cons_run(kp_ctx* ctx, int m0, int m1, int s0, int s1, kp_probe_
         k.ov_slot = c->d_ov_slot.p;
         k.ov_hdr = c->d_ov_hdr.p;
         k.ov_words = c->d_ov_words.p;
+        k.pov_cap = std::max(1, k.ring_cap);  // host ports: one overlay entry per pod a probe can place
+        if (d.PW > 0) {
+            HIPCHK(c->d_pov_node.ensure((size_t)fw * k.pov_cap));
+            HIPCHK(c->d_pov_mask.ensure((size_t)fw * k.pov_cap * d.PW));
+            k.pov_node = c->d_pov_node.p;
+            k.pov_mask = c->d_pov_mask.p;
+        }
     }
     k.pbits = c->d_pbits.p;
     k.next_probe = c->d_next.p;

@@ -54,6 +54,7 @@ __global__ __launch_bounds__(256) void existing_init_kernel(KpDev d) {
         if (av < 0 || (!act && rq > av)) ok = false;
     }
     d.ex_static[j] = ok ? 1 : 0;
+    for (int pw = 0; pw < d.PW; pw++) d.ex_ports[(size_t)j * d.PW + pw] = d.ex_ports0[(size_t)j * d.PW + pw];  // bound pods' host ports
     for (int ai = 0; ai < d.n_active; ai++) {
         const int r = act_axis(d, ai);
         d.ex_head[(size_t)ai * d.E + j] = d.ex_avail[(size_t)j * d.R + r] - d.ex_req[(size_t)j * d.R + r];
@@ -65,6 +66,8 @@ __global__ __launch_bounds__(64) void existing_mask_kernel(KpDev d) {
     const int w = blockIdx.x, c = blockIdx.y, lane = threadIdx.x, j = w * 64 + lane;
     bool bit = j < d.E && d.ex_static[j] && ((d.ex_tol[(size_t)c * d.EW + w] >> lane) & 1ull);
     if (bit) bit = node_compatible(d, d.ex_hdr0 + (size_t)j * d.K, d.ex_words0 + (size_t)j * d.DW, c);
+    // host ports: ExistingNode.Add fails when a port of the class meets a port of the pods bound to the node
+    for (int pw = 0; pw < d.PW && bit; pw++) bit = !(d.ex_ports0[(size_t)j * d.PW + pw] & d.cls_ports[(size_t)c * d.PW + pw]);
     const uint64_t m = ballot(bit);
     if (lane == 0) d.XT[(size_t)c * d.EW + w] = m;
 }
@@ -141,6 +144,15 @@ KP_FFD_DECL(ffd_pref_hbm_kernel)
 KP_FFD_DECL(ffd_pref_topo_hbm_kernel)
 KP_FFD_DECL(ffd_pref_resv_hbm_kernel)
 KP_FFD_DECL(ffd_pref_resv_topo_hbm_kernel)
+// host ports (ffd_solve PORTS, with PREF on): kp_ffd_ports{,_resv}{,_topo}.hip
+KP_FFD_DECL(ffd_ports_kernel)
+KP_FFD_DECL(ffd_ports_topo_kernel)
+KP_FFD_DECL(ffd_ports_resv_kernel)
+KP_FFD_DECL(ffd_ports_resv_topo_kernel)
+KP_FFD_DECL(ffd_ports_hbm_kernel)
+KP_FFD_DECL(ffd_ports_topo_hbm_kernel)
+KP_FFD_DECL(ffd_ports_resv_hbm_kernel)
+KP_FFD_DECL(ffd_ports_resv_topo_hbm_kernel)
 #undef KP_FFD_DECL
 // [diagnostic twin][HBM * 8 + PREF * 4 + RESV * 2 + TOPO]
 typedef void (*FfdKernel)(KpDev);
@@ -151,6 +163,12 @@ typedef void (*FfdKernel)(KpDev);
      ffd_pref_hbm_kernel##sfx, ffd_pref_topo_hbm_kernel##sfx, ffd_pref_resv_hbm_kernel##sfx, ffd_pref_resv_topo_hbm_kernel##sfx}
 static const FfdKernel kFfdKernels[2][16] = {KP_FFD_ROW(), KP_FFD_ROW(_prof)};
 #undef KP_FFD_ROW
+// solves with host ports: [diagnostic twin][HBM * 4 + RESV * 2 + TOPO]
+#define KP_FFD_PORTS_ROW(sfx)                                                                                            \
+    {ffd_ports_kernel##sfx,     ffd_ports_topo_kernel##sfx,     ffd_ports_resv_kernel##sfx,     ffd_ports_resv_topo_kernel##sfx, \
+     ffd_ports_hbm_kernel##sfx, ffd_ports_topo_hbm_kernel##sfx, ffd_ports_resv_hbm_kernel##sfx, ffd_ports_resv_topo_hbm_kernel##sfx}
+static const FfdKernel kFfdPortsKernels[2][8] = {KP_FFD_PORTS_ROW(), KP_FFD_PORTS_ROW(_prof)};
+#undef KP_FFD_PORTS_ROW
 
 
 // ------------------------------------------------------------------------------------------------
@@ -461,6 +479,11 @@ hipError_t kp_ffd_set_attributes() {
             const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS_BYTES);
             if (e != hipSuccess) return e;
         }
+    for (const auto& row : kFfdPortsKernels)
+        for (const FfdKernel k : row) {
+            const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS_BYTES);
+            if (e != hipSuccess) return e;
+        }
     return hipSuccess;
 }
 hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s) {
@@ -471,7 +494,9 @@ hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s) {
     const bool pref = d.relax_next || d.best_effort;
     // KPSIM_PROFILE / KPSIM_TRACE_POD: the diagnostic twin (the production kernels carry no stamps, n_* counters or trace)
     const int twin = (d.profile || d.trace) ? 1 : 0;
-    const FfdKernel k = kFfdKernels[twin][(d.slice_hbm ? 8 : 0) + (pref ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)];
+    // a solve with host ports (PW > 0) runs its own instantiations; every other solve the entry point it always had
+    const FfdKernel k = d.PW > 0 ? kFfdPortsKernels[twin][(d.slice_hbm ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)]
+                                 : kFfdKernels[twin][(d.slice_hbm ? 8 : 0) + (pref ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)];
     hipLaunchKernelGGL(k, g, b, bytes, s, d);
     return hipGetLastError();
 }

@@ -51,6 +51,7 @@
 #define KP_CC_REC 16                 // recording groups a ClassCache holds (the rest are read from cls_tr)
 #define KP_CC_TC 16                  // constraining groups a ClassCache holds (the rest are read from cls_tc)
 #define KP_MAX_TOPO_KEYS 8           // distinct value-keyed topology keys among a class's constraining groups
+#define KP_MAX_PORT_WORDS 4          // u64 words of a host-port mask: the port-bit dictionary of one solve (256 bits)
 #define KP_TRACE_N 16384             // diagnostics ring (KPSIM_TRACE_*)           // topology groups recording one pod class's placements
 
 // cls_flags bits
@@ -61,6 +62,7 @@
 #define CF_TOPO_CONS 16u             // constrained by some group (AddRequirements runs in NodeClaim.Add)
 #define CF_TOPO_QREC 32u             // every recording group's node filter is decidable from a NodeClaim's template
                                      // alone (no node-affinity filter owned by another class): quick accepts record
+#define CF_PORTS 64u                 // carries host ports (cls_ports row non-zero): never quick-accepted or batched
 
 // tg_info.x
 #define TG_TYPE 3                    // KP_TOPO_SPREAD / AFFINITY / ANTI_AFFINITY
@@ -328,6 +330,17 @@ struct KpDev {
     // a device copy of this struct (uploaded before each FFD launch): out-of-line device functions take it instead of
     // the kernel argument, whose address would otherwise escape and put every field read of the kernel in scratch
     const KpDev* self;
+
+    // ---------------- host ports ([core] scheduling/hostportusage.go; DESIGN.md §4 "Host ports") ----------------
+    // Masks over the solve's port-bit dictionary (kp_host.cpp solve_host_ports): two port sets conflict iff their masks
+    // meet.  PW == 0: no host ports anywhere in the input (the other fields are unset).  Kept behind every older
+    // field: the port-free entry points read theirs at the kernel-argument offsets they always had.
+    int32_t PW;                      // mask words (<= KP_MAX_PORT_WORDS)
+    const uint64_t* cls_ports;       // [C][PW] ports of a pod of the class (relaxation stages: their input class's)
+    const uint64_t* tmpl_ports;      // [NT][PW] daemonHostPortUsage: a new NodeClaim of the template starts with these
+    const uint64_t* ex_ports0;       // [E][PW] ports of the pods bound to the node
+    uint64_t* ex_ports;              // [E][PW] working copy: + the port pods this solve placed on the node
+    uint64_t* nc_ports;              // [NCcap][PW] used ports of the in-flight NodeClaims
 };
 
 // stats slots

@@ -102,13 +102,24 @@ class kp_existing_node(C.Structure):
                 ("requests", c_int64_p)]
 
 
+KP_PROTO_TCP, KP_PROTO_UDP, KP_PROTO_SCTP = 0, 1, 2
+PROTOCOLS = {"TCP": KP_PROTO_TCP, "UDP": KP_PROTO_UDP, "SCTP": KP_PROTO_SCTP}
+
+
+class kp_host_port(C.Structure):
+    _fields_ = [("ip", C.c_char_p), ("protocol", C.c_int32), ("port", C.c_int32)]
+
+
 class kp_solve_input(C.Structure):
     _fields_ = [("n_nodepools", C.c_int32), ("nodepools", C.POINTER(kp_nodepool)),
                 ("n_classes", C.c_int32), ("classes", C.POINTER(kp_pod_class)),
                 ("pods", kp_pods_view),
                 ("n_existing", C.c_int32), ("existing", C.POINTER(kp_existing_node)),
                 ("max_instance_types", C.c_int32), ("min_values_policy", C.c_int32),
-                ("n_bound", C.c_int32), ("bound_node", c_int32_p), ("bound_class", c_int32_p)]
+                ("n_bound", C.c_int32), ("bound_node", c_int32_p), ("bound_class", c_int32_p),
+                ("class_port_offsets", c_int32_p), ("class_ports", C.POINTER(kp_host_port)),
+                ("nodepool_port_offsets", c_int32_p), ("nodepool_ports", C.POINTER(kp_host_port)),
+                ("existing_port_offsets", c_int32_p), ("existing_ports", C.POINTER(kp_host_port))]
 
 
 class kp_solve_stats(C.Structure):
@@ -294,3 +305,31 @@ def topology_array(keep, terms):
         x.namespaces = keep.cstrs(list(t.namespaces))
     keep.hold(arr)
     return len(terms), arr
+
+
+def host_port_csr(keep, rows):
+    """rows: one list of model.HostPort per class / NodePool / node -> (offsets pointer, entries pointer), the CSR
+    side table of kp_solve_input; (None, None) when every row is empty (the ABI's "none")."""
+    rows = [list(r) for r in rows]
+    if not any(rows):
+        return None, None
+    off = np.zeros(len(rows) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(r) for r in rows])
+    arr = (kp_host_port * max(1, int(off[-1])))()
+    i = 0
+    for r in rows:
+        for hp in r:
+            arr[i].ip = keep.hold((hp.ip or "").encode())
+            arr[i].protocol = PROTOCOLS[hp.protocol]
+            arr[i].port = int(hp.port)
+            i += 1
+    keep.hold(arr)
+    return keep.ptr(off, np.int32, C.c_int32), C.cast(arr, C.POINTER(kp_host_port))
+
+
+def host_port_rows(offsets, entries, n):
+    """The inverse of host_port_csr over a kp_solve_input's fields: n lists of (ip, protocol, port) tuples."""
+    if not offsets:
+        return [[] for _ in range(n)]
+    return [[((entries[i].ip or b"").decode(), int(entries[i].protocol), int(entries[i].port))
+             for i in range(offsets[r], offsets[r + 1])] for r in range(n)]

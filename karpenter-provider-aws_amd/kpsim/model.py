@@ -97,6 +97,14 @@ class InstanceType:
 
 
 @dataclass
+class HostPort:
+    """One container port with hostPort != 0 (kpsim.h kp_host_port).  ip "", "0.0.0.0" or "::" is unspecified."""
+    port: int
+    protocol: str = "TCP"                       # TCP | UDP | SCTP
+    ip: str = ""
+
+
+@dataclass
 class NodePool:
     name: str
     weight: int = 0
@@ -106,6 +114,7 @@ class NodePool:
     daemon_overhead: Optional[np.ndarray] = None      # [R] milli
     limits_remaining: Optional[Dict[str, int]] = None  # resource -> remaining milli
     instance_types: Optional[List[int]] = None         # catalog rows; None = all
+    daemon_host_ports: List[HostPort] = field(default_factory=list)  # host ports of the pool's daemonset pods
 
     def template_requirements(self):
         """NewNodeClaimTemplate: spec requirements + template labels + karpenter.sh/nodepool In [name]."""
@@ -149,6 +158,7 @@ class PodClass:
     topology: List[TopologyTerm] = field(default_factory=list)
     required_terms: List[List[Requirement]] = field(default_factory=list)
     preferred_terms: List[Tuple[int, List[Requirement]]] = field(default_factory=list)
+    host_ports: List[HostPort] = field(default_factory=list)
 
 
 @dataclass
@@ -170,6 +180,7 @@ class ExistingNode:
     available: np.ndarray
     requests: Optional[np.ndarray] = None
     taints: List[Taint] = field(default_factory=list)
+    host_ports: List[HostPort] = field(default_factory=list)   # host ports of every pod bound to the node
 
 
 @dataclass
@@ -355,6 +366,9 @@ class SolveInputView:
             b = np.array(prob.bound, np.int32).reshape(-1, 2)
             v.bound_node = k.ptr(b[:, 0].copy(), np.int32, C.c_int32)
             v.bound_class = k.ptr(b[:, 1].copy(), np.int32, C.c_int32)
+        v.class_port_offsets, v.class_ports = abi.host_port_csr(k, [pc.host_ports for pc in prob.classes])
+        v.nodepool_port_offsets, v.nodepool_ports = abi.host_port_csr(k, [n.daemon_host_ports for n in prob.nodepools])
+        v.existing_port_offsets, v.existing_ports = abi.host_port_csr(k, [e.host_ports for e in prob.existing])
 
 
 @dataclass
