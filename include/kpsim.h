@@ -362,8 +362,13 @@ kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out);
  * templates, -, full-pdqsort share; [11..15] per-stage evaluation cycles; [20..23] fast-loop cycles: pop, scan, quick
  * check, quick commit; [24..34] fast-loop event counts (n_*); [36..37] topology prefilter setup / scan cycles;
  * [42..45] cycles of wave 0's hand-off of a pod to the block: fast-loop entry up to the first pop, the quick check
- * that failed, window flush + candidate collection, statistics write-back + the wait for the flushed totals
- * (n up to 46). */
+ * that failed, window flush + candidate collection, statistics write-back + the wait for the flushed totals;
+ * [46..48] wave 0's same-shape inner loop: pods it took without a pass through the general loop, the cycles of its
+ * steps (from the end of one batch to the next check), and the steps that placed several pods on one NodeClaim at
+ * once.  The fast-loop event counts keep their meaning: n_batches, n_noinv and n_winmove count what the general loop
+ * would have counted for the same pods, whichever loop handled them (a step of j pods counts j batches and j
+ * "no inversion" sorts), so batches - inner-loop pods + slow-path pods = entries to the general loop; [22] quick check
+ * holds the checks and batches of both loops (n up to 49). */
 kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n);
 
 /*

@@ -816,12 +816,17 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
     const long long pop_bound = (long long)P * 64 + 4096;  // Go's loop ends within P·(retries+1) pops
     // wave 0 state that lives across slow-path episodes:
     //   queue window — lane i holds the i-th next queued pod (refilled every 64 pops; pushes land after it):
-    //     pod, class, shape, lastLen, tolerations word (bit 31: class has no requirement keys), and
-    //     vq[a] = ceil(request[axis a] >> qshift[a]) for the quick-accept axes (clamped to int32).
+    //     pod, class, shape, lastLen: what every pop reads.  What only a change of shape needs (the class's tolerations
+    //     word, the scaled quick-accept requests) is derived there, from the class and the window's request rows in LDS
+    //     (qw_req), and not carried in eight more registers through every episode of the block.
+    //   The 8-wave PORTS instantiations keep the wider window (vtol, vq) and take no inner loop (LEAN below): they sit
+    //   at 247-254 of 256 VGPRs with ~770 spilled SGPRs, and either change made them spill the VGPRs that hold those
+    //   SGPRs; their code is the one they had.
+    constexpr bool LEAN = !PORTS || TOPO;
     int qw_n = 0, qw_used = 0;
     int vp = 0, vc = 0, vshape = 0, vlast = 0;
-    uint64_t vtol = 0;
-    int32_t vq[KP_LDS_AXES];
+    uint64_t vtol = 0;             // PORTS: tolerations word of the pod's class (bit 63: no requirement keys)
+    int32_t vq[KP_LDS_AXES];       // PORTS: the scaled quick-accept requests (pq below) of the pod
 #pragma unroll
     for (int ai = 0; ai < KP_LDS_AXES; ai++) vq[ai] = 0;
 
@@ -880,7 +885,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             long long popped = S.st[ST_POPPED], scanned = 0, nquick = 0, sfast = 0, sfull = 0, csort = 0, csfull = 0;
             long long cqpop = 0, cqscan = 0, cqcheck = 0, cqcommit = 0;
             long long n_noinv = 0, n_winmove = 0, n_ldssort = 0, n_pivot = 0, n_winload = 0, n_flush = 0, n_shape = 0;
-            long long n_r2 = 0, n_rwb = 0, n_rout = 0, n_batch = 0;
+            long long n_r2 = 0, n_rwb = 0, n_rout = 0, n_batch = 0, n_inner = 0, n_multi = 0, cqinner = 0;
             long long ho_entry = -1, ho_fail = 0, t_f = 0;  // PROF: the hand-off's parts (ST_HANDOFF)
 
             // ---- slice window: lane i mirrors slice position wb + i and its NodeClaim (authoritative while valid) ----
@@ -937,6 +942,28 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 wa = q < N && absorbed(wm);
                 wcnt = 0;
             };
+            // pdqsort's stable move of the changed element at window lane fl to the end e - 1 of its old run (el = e - wb):
+            // [f, e-1) <- [f+1, e), e-1 <- the changed element (registers move along)
+            auto win_move = [&](int fl, int el) {
+                const bool sh = lane >= fl && lane < el - 1, last = lane == el - 1;
+                auto mv = [&](auto& x) {
+                    using X = std::remove_reference_t<decltype(x)>;
+                    const int xf = rl32((int)x, fl);
+                    // lane i <- lane i+1 with a DPP wavefront shift (wave_shl:1) instead of an LDS
+                    // permute; lane 63's result is unused (sh requires lane < el - 1 <= 63)
+                    const int nx = __builtin_amdgcn_update_dpp(0, (int)x, 0x130, 0xF, 0xF, false);
+                    x = sh ? (X)nx : (last ? (X)xf : x);
+                };
+                mv(wk);
+                mv(wo);
+                mv(wm);
+                mv(wcnt);
+#pragma unroll
+                for (int ai = 0; ai < KP_LDS_AXES; ai++) mv(wh[ai]);
+                int wai = wa ? 1 : 0;
+                mv(wai);
+                wa = wai != 0;
+            };
             int resume = TOPO_ON ? S.topo_resume : 0;  // the current pod comes back from the block for the sort
             for (;;) {
               int p, off, shape;
@@ -967,13 +994,15 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         vc = d.pod_cls[vp];
                         vshape = d.pod_shape[vp];
                         vlast = (PREF && d.last_ep && d.last_ep[vp] != ep) ? -1 : d.last_len[vp];
-                        vtol = (d.tol[vc] & ~(1ull << 63)) | ((d.cls_flags[vc] & 4u) ? (1ull << 63) : 0ull);
                         for (int r = 0; r < R; r++) qw_req[lane * R + r] = d.pod_req[(size_t)vp * R + r];
+                        if constexpr (!LEAN) {
+                            vtol = (d.tol[vc] & ~(1ull << 63)) | ((d.cls_flags[vc] & 4u) ? (1ull << 63) : 0ull);
 #pragma unroll
-                        for (int ai = 0; ai < KP_LDS_AXES; ai++) {
-                            const int64_t pr = ai < A ? d.pod_req[(size_t)vp * R + d.active_axes[ai]] : 0;
-                            const int64_t x = (pr + ((1ll << d.qshift[ai]) - 1)) >> d.qshift[ai];
-                            vq[ai] = x > 0x7FFFFFFF ? 0x7FFFFFFF : (int32_t)x;
+                            for (int ai = 0; ai < KP_LDS_AXES; ai++) {
+                                const int64_t pr = ai < A ? d.pod_req[(size_t)vp * R + d.active_axes[ai]] : 0;
+                                const int64_t x = (pr + ((1ll << d.qshift[ai]) - 1)) >> d.qshift[ai];
+                                vq[ai] = x > 0x7FFFFFFF ? 0x7FFFFFFF : (int32_t)x;
+                            }
                         }
                     }
                     qw_n = wn;
@@ -1005,11 +1034,27 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         any_rej = 0;
                     }
                     c = rl32(vc, off);
-                    ctopo = TOPO_ON && (d.cls_flags[c] & CF_TOPO) != 0;
-                    cport = PORTS && (d.cls_flags[c] & CF_PORTS) != 0;
-                    tl = rl64(vtol, off);
+                    if constexpr (LEAN) {
+                        const uint32_t cfl = d.cls_flags[c];
+                        ctopo = TOPO_ON && (cfl & CF_TOPO) != 0;
+                        cport = PORTS && (cfl & CF_PORTS) != 0;
+                        // tolerations word of the class (bit 63: the class has no requirement keys)
+                        tl = (d.tol[c] & ~(1ull << 63)) | ((cfl & 4u) ? (1ull << 63) : 0ull);
+                        // pq[a] = ceil(request[axis a] >> qshift[a]) for the quick-accept axes (clamped to int32)
 #pragma unroll
-                    for (int ai = 0; ai < KP_LDS_AXES; ai++) pq[ai] = rl32(vq[ai], off);
+                        for (int ai = 0; ai < KP_LDS_AXES; ai++) {
+                            const int64_t pr = ai < A ? qw_req[off * R + d.active_axes[ai]] : 0;
+                            const int64_t x = (pr + ((1ll << d.qshift[ai]) - 1)) >> d.qshift[ai];
+                            // (an LDS read is a vector value to the compiler: back to a scalar register, as the readlane was)
+                            pq[ai] = __builtin_amdgcn_readfirstlane(x > 0x7FFFFFFF ? 0x7FFFFFFF : (int32_t)x);
+                        }
+                    } else {
+                        ctopo = TOPO_ON && (d.cls_flags[c] & CF_TOPO) != 0;
+                        cport = PORTS && (d.cls_flags[c] & CF_PORTS) != 0;
+                        tl = rl64(vtol, off);
+#pragma unroll
+                        for (int ai = 0; ai < KP_LDS_AXES; ai++) pq[ai] = rl32(vq[ai], off);
+                    }
                     {
                         sreq = lane < R ? qw_req[off * R + lane] : 0;
                         if (lane < R) S.shape_req[lane] = sreq;
@@ -1123,27 +1168,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                                 }
                             }
                             if (fast) {
-                                // stable move: [f, e-1) <- [f+1, e), e-1 <- the changed element (registers move along)
-                                const bool sh = lane >= fl && lane < el - 1, last = lane == el - 1;
-                                auto mv = [&](auto& x) {
-                                    using X = std::remove_reference_t<decltype(x)>;
-                                    const int xf = rl32((int)x, fl);
-                                    // lane i ← lane i+1 with a DPP wavefront shift (wave_shl:1) instead of an LDS
-                                    // permute; lane 63's result is unused (sh requires lane < el - 1 <= 63)
-                                    const int nx = __builtin_amdgcn_update_dpp(0, (int)x, 0x130, 0xF, 0xF, false);
-                                    x = sh ? (X)nx : (last ? (X)xf : x);
-                                };
-                                mv(wk);
-                                mv(wo);
-                                mv(wm);
-                                mv(wcnt);
-#pragma unroll
-                                for (int ai = 0; ai < KP_LDS_AXES; ai++) mv(wh[ai]);
-                                {
-                                    int wai = wa ? 1 : 0;
-                                    mv(wai);
-                                    wa = wai != 0;
-                                }
+                                win_move(fl, el);
                                 how = 1;
                                 n_winmove++;
                                 done_here = true;
@@ -1200,8 +1225,12 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     }
                     pos = wb + 64;
                 }
-                const long long t_d = prof_clock(prof);
+                long long t_d = prof_clock(prof);
                 cqscan += t_d - t_c;
+                // an episode of same-shape pods (the inner loop): the check of one pod at f, its batch,
+                // then the pending move and the next pod's f without a pass through the general loop
+                bool again = false;  // the episode ended with the next pod not popped: the general loop takes over
+                for (;;) {
                 if (f < N && !(PORTS && cport)) {  // a port-carrying pod is never quick-accepted: the block takes it
                     const int fl = f - wb;
                     bool wfit = A > 0;  // no witness table (A == 0): every pod is evaluated
@@ -1358,9 +1387,99 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         n_batch++;
                         const long long t_e = prof_clock(prof);
                         cqcheck += t_e - t_d;
+                        // ---- the next pods of the episode.  A pod stays here when the general loop would do nothing for
+                        // it but the pending move of the element at f inside the window and the scan from f: it is the next
+                        // entry of the queue window, of the same shape (so the same class: not a topology or port pod, no
+                        // rejection memo to clear), lastLen does not end the Solve, and no existing node is left to try.
+                        // Whatever else (a window refill, a shape change, a run that leaves the window, a choosePivot
+                        // sample at f, 12 < N < 50 with an inversion) goes back to the general loop with the pod not
+                        // popped and dkind / dpos / sstart as that loop expects them: 1 / f / f before the move, 0 after.
+                        again = true;
+                        if (!LEAN || wb < 0 || xstart < d.E || popped + 64 >= pop_bound) break;
+                        bool stay = false;
+                        for (;;) {
+                            if (qw_used >= qw_n) break;
+                            const int noff = qw_used;
+                            // the same-shape pods at the head of the queue window (lastLen termination checked per pod)
+                            const uint64_t nsm = ~(ballot(lane >= noff && lane < qw_n && vshape == shape &&
+                                                          vlast != qcount - (lane - noff)) >> noff);
+                            const int nnp = nsm ? __builtin_ctzll(nsm) : 64;
+                            if (nnp == 0) break;
+                            const int nfl = f - wb;
+                            const uint32_t nkv = (uint32_t)rl32((int)wk, nfl) & KEYMASK;  // key[f], already incremented
+                            const uint64_t nge = ballot(lane > nfl && (wb + lane >= N || (wk & KEYMASK) >= nkv));
+                            if (nge == 0 && wb + 64 < N) break;  // the run leaves the window
+                            const int nel = nge ? __ffsll((unsigned long long)nge) - 1 : N - wb;  // run end e - wb
+                            if (nel == nfl + 1) {
+                                // key[f+1] >= key[f]: no inversion, the element stays at f.  While its key stays below
+                                // key[f+1] its run has length 1, so each of the next pods is a batch of one on it followed
+                                // by the same "no inversion": j of them are placed in one step when the witness fits j times
+                                // (lane noff + i holds pod i of the step in its queue-window registers)
+                                const int gap = f + 1 < N ? (int)(((uint32_t)rl32((int)wk, (nfl + 1) & 63) & KEYMASK) - nkv) : 64;
+                                const int j = nnp < gap ? nnp : gap;
+                                // (uniform arithmetic on the headroom of lane nfl: no vector temporaries)
+                                bool fitj = A > 0 && j > 0 && ((ballot(wa && !(wk >> 31)) >> nfl) & 1ull);
+#pragma unroll
+                                for (int ai = 0; ai < KP_LDS_AXES; ai++)
+                                    if (ai < A) fitj = fitj && (long long)pq[ai] * j <= (long long)rl32(wh[ai], nfl);
+                                if (fitj) {
+                                    const int nc = rl32((int)wo, nfl), pi = lane - noff;
+                                    if (pi >= 0 && pi < j) {
+                                        d.pod_result[vp] = nc;
+                                        d.pod_order[vp] = seq + pi;
+                                    }
+                                    if (lane == nfl) {
+#pragma unroll
+                                        for (int ai = 0; ai < KP_LDS_AXES; ai++) wh[ai] -= pq[ai] * j;
+                                        wk += j;
+                                        wcnt += j;
+                                    }
+                                    seq += j;
+                                    nquick += j;
+                                    qw_used += j;
+                                    qhead += j;
+                                    if (qhead >= P) qhead -= P;
+                                    qcount -= j;
+                                    popped += j;
+                                    scanned += (long long)N * j;
+                                    n_noinv += j;
+                                    n_batch += j;
+                                    n_inner += j;
+                                    n_multi++;
+                                    continue;  // the element at f gained j pods: its move is pending as after a batch
+                                }
+                                n_noinv++;
+                            } else {
+                                if (!movable) break;  // the general loop: pivot hint or pdqsort
+                                win_move(nfl, nel);
+                                sfast++;
+                                n_winmove++;
+                            }
+                            dkind = 0;
+                            const uint64_t nm = ballot(lane >= nfl && !(wk >> 31));  // positions >= N carry bit 31
+                            if (!nm) break;  // every window position from f on has rejected the shape: the general scan
+                            f = wb + __ffsll((unsigned long long)nm) - 1;
+                            off = noff;
+                            p = rl32(vp, off);
+                            qw_used++;
+                            qhead = qhead + 1 == P ? 0 : qhead + 1;
+                            qcount--;
+                            popped++;
+                            scanned += N;
+                            n_inner++;
+                            stay = true;
+                            break;
+                        }
+                        t_d = prof_clock(prof);
+                        cqinner += t_d - t_e;
+                        if (!stay) break;
+                        again = false;
                         continue;
                     }
                 }
+                break;
+                }
+                if (again) continue;
                 // slow path: the whole block evaluates this pod
                 t_f = prof_clock(prof);
                 ho_fail = t_f - t_d;
@@ -1427,6 +1546,9 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     S.st[ST_N_SHAPE + 2] += n_rwb;
                     S.st[ST_N_SHAPE + 3] += n_rout;
                     S.st[ST_N_SHAPE + 4] += n_batch;
+                    S.st[ST_N_INNER] += n_inner;
+                    S.st[ST_CYC_QINNER] += cqinner;
+                    S.st[ST_N_MULTI] += n_multi;
                     // the hand-off to the block, by part: entry up to the first pop; the quick check that failed; the
                     // window flush and the candidate collection (the write-back and its wait are stamped below)
                     S.st[ST_HANDOFF] += ho_entry < 0 ? 0 : ho_entry;

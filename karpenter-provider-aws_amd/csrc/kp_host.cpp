@@ -429,7 +429,7 @@ struct kp_ctx {
     double ns_prep = 0, ns_exec = 0, ns_fin = 0;
     hipEvent_t ev[6] = {};
     double kernel_ms[5] = {};
-    int64_t cycles[41] = {};  // FFD phases (s_memtime): pop, sort, scan+eval, templates, commit, full pdqsort
+    int64_t cycles[44] = {};  // FFD phases (s_memtime): pop, sort, scan+eval, templates, commit, full pdqsort
     bool any_min_values = false;             // some template requirement carries minValues
     int max_min_values = 0;                  // the largest minValues among the template requirements
     bool min_multi = false;                  // ... on a multi-valued catalog key (zone, capacity type, ...)
@@ -3493,6 +3493,9 @@ extern "C" kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out) {
     for (int i = 0; i < 4; i++) c->cycles[33 + i] = st[ST_REJ_REQ + i];
     for (int i = 0; i < 3; i++) c->cycles[37 + i] = st[ST_HANDOFF + i];
     c->cycles[40] = st[ST_HANDOFF_WB];
+    c->cycles[41] = st[ST_N_INNER];
+    c->cycles[42] = st[ST_CYC_QINNER];
+    c->cycles[43] = st[ST_N_MULTI];
     if (getenv("KPSIM_PROFILE") && st[ST_SLOW_WHY] + st[ST_SLOW_WHY + 1] + st[ST_SLOW_WHY + 2] + st[ST_SLOW_WHY + 3])
         fprintf(stderr, "[kpsim] slow-path pods: no candidate %lld, class not absorbed %lld, witness short %lld, no witness table %lld; "
                 "no-op merge quick accepts %lld; placed by the first candidate %lld, a later one %lld, the templates %lld; "
@@ -3544,7 +3547,7 @@ extern "C" kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n) {
     if (!ctx || !ms) return KP_E_INVALID;
     if (!ctx->executed) return fail(ctx, KP_E_STATE, "no execute yet");
     for (int i = 0; i < n && i < 5; i++) ms[i] = ctx->kernel_ms[i];
-    for (int i = 5; i < n && i < 46; i++) ms[i] = (double)ctx->cycles[i - 5];
+    for (int i = 5; i < n && i < 49; i++) ms[i] = (double)ctx->cycles[i - 5];
     return KP_OK;
 }
 

@@ -18,7 +18,10 @@ NAMES = ["cyc_fast_loop", "cyc_sort", "cyc_slow_eval", "cyc_templates", "-", "cy
          "n_flush", "n_shape", "n_lds_append", "n_lds_nowin", "n_lds_outside", "n_batches", "topo_quick",
          "cyc_topo_setup", "cyc_topo_scan", "rej_requirements", "rej_topology", "rej_types", "rej_min_values",
          # wave 0's hand-off of a pod to the block, by part (kp_layout.h ST_HANDOFF)
-         "cyc_ho_entry", "cyc_ho_failed_check", "cyc_ho_flush_collect", "cyc_ho_writeback"]
+         "cyc_ho_entry", "cyc_ho_failed_check", "cyc_ho_flush_collect", "cyc_ho_writeback",
+         # wave 0's same-shape inner loop (kp_layout.h ST_N_INNER): pods it took without a pass through the general loop
+         # and the cycles of their steps; cyc_q_check holds the checks and batches of both loops
+         "n_inner", "cyc_q_inner", "n_multi"]
 
 
 def ffd_counters(ctx):
@@ -46,8 +49,11 @@ def main():
     wall = (time.perf_counter() - t) * 1e3
     r = out.results()
     kt = ctx.kernel_times_ms()
+    ffd = dict(zip(NAMES, ffd_counters(ctx)))
+    # entries to wave 0's general loop: one per batch that the inner loop did not start, one per pod handed to the block
+    ffd["general_loop_entries"] = ffd["n_batches"] - ffd["n_inner"] + ffd["slow_pods"]
     print(json.dumps({"config": which, "pods": n, "wall_ms": wall, "kernel_ms": kt, "nodeclaims": r.n_nodeclaims, "stats": r.stats,
-                      "ffd": dict(zip(NAMES, ffd_counters(ctx)))}, indent=1))
+                      "ffd": ffd}, indent=1))
     ctx.close()
 
 
