@@ -233,6 +233,26 @@ typedef struct kp_host_port {
     int32_t port;                            /* hostPort, != 0 */
 } kp_host_port;
 
+/*
+ * Volume attach limits ([core] scheduling/volumeusage.go and existingnode.go, recalled; restated in DESIGN.md §4
+ * "Volume limits").  A pod's volumes are driver -> set of claim ids (the PVC's namespace/name, or pod-name-volume for a
+ * generic ephemeral volume; the caller resolves claim -> CSI driver, a claim without a driver has no entry).  A node
+ * holds the claim sets of its bound pods and, per driver, the CSINode's Allocatable.Count; a driver without a limit on
+ * a node is unlimited there.  ExistingNode.Add fails when, for some driver k of node.volumes ∪ pod.volumes with a limit
+ * on the node, |node.volumes[k] ∪ pod.volumes[k]| > limit[k].  It is a set union: a claim the node already mounts
+ * costs the pod nothing there.  The loop runs over the union's drivers, so a node already over a limit refuses every
+ * pod, also one without volumes.  A successful Add inserts the pod's claims into the node's sets, a failed one changes
+ * nothing.  NodeClaim.Add and the templates have no volume check (a new NodeClaim has no CSINode yet).
+ */
+typedef struct kp_volume {
+    int32_t driver;                          /* index into volume_drivers */
+    int32_t id;                              /* the caller's dense claim id (>= 0); equal ids are the same claim */
+} kp_volume;
+typedef struct kp_volume_limit {
+    int32_t driver;                          /* index into volume_drivers */
+    int32_t limit;                           /* CSINode Allocatable.Count, >= 0 */
+} kp_volume_limit;
+
 typedef struct kp_solve_input {
     int32_t n_nodepools;
     const kp_nodepool* nodepools;
@@ -260,6 +280,22 @@ typedef struct kp_solve_input {
                                                 (StateNode.HostPortUsage()); in a kp_consolidate_input this includes the
                                                 reschedulable pods of candidates, as `available` already does */
     const kp_host_port* existing_ports;
+    /* Volume attach limits, as three CSR side tables; a NULL offsets array means "none", so a zero-initialised input
+       behaves as one without volumes.  Drivers without a limit on any node are dropped at prepare.  KP_E_INVALID: a
+       driver index out of range, a negative id or limit, a duplicate (driver, id) or a driver listed twice in one row,
+       one id under two drivers.  KP_E_UNSUPPORTED (never approximated): more than 8 drivers with a limit somewhere in
+       the input, or more than 256 shared claims (claims of limited drivers referenced by two or more pods of the
+       input, or by a pod and by a node). */
+    int32_t n_volume_drivers;
+    const char* const* volume_drivers;       /* [n_volume_drivers] CSI driver names (used in messages only; may be NULL) */
+    const int32_t* pod_volume_offsets;       /* [n_pods+1] or NULL: the pod's claims */
+    const kp_volume* pod_volumes;
+    const int32_t* existing_volume_offsets;  /* [n_existing+1] or NULL: the claims of all pods bound to the node; in a
+                                                kp_consolidate_input this includes the reschedulable pods of candidates,
+                                                as `available` and the port tables do */
+    const kp_volume* existing_volumes;
+    const int32_t* existing_limit_offsets;   /* [n_existing+1] or NULL: the node's per-driver attach limits */
+    const kp_volume_limit* existing_limits;
 } kp_solve_input;
 
 /* Per-solve counters: evaluation counts feed the algorithmic-bytes roofline. */
@@ -372,6 +408,17 @@ kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out);
 kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n);
 
 /*
+ * Diagnostics: the volume encoding of the prepared Solve or consolidation pass (what kp_solve_prepare /
+ * kp_consolidate_prepare derived from the volume tables), copied into buf as int64 values; *needed receives the
+ * length, KP_E_BUFFER when cap is smaller.  Layout: VD (limited drivers), VW (mask words), shared bits, NS
+ * (signatures), P, E; then limited_driver[VD] (index into volume_drivers), pod_signature[P], signature_count[NS][VD]
+ * (private claims), signature_mask[NS][VW] (shared claims, uint64 bit patterns), driver_mask[VD][VW],
+ * node_count[VD][E], node_limit[VD][E] (INT32_MAX: none), node_mask[E][VW], node_over_limit[E].  VD == 0 (no limited
+ * driver in the input): the header alone, with P = E = 0.
+ */
+kp_status kp_solve_volume_encoding(kp_ctx* ctx, int64_t* buf, int64_t cap, int64_t* needed);
+
+/*
  * Consolidation re-simulation — replaces the scheduling simulation of [core] pkg/controllers/disruption:
  * SimulateScheduling (helpers.go) + consolidation.computeConsolidation (consolidation.go), driven by
  * SingleNodeConsolidation (singlenodeconsolidation.go: first valid candidate in disruption-cost order) and
@@ -420,7 +467,9 @@ typedef struct kp_consolidate_input {
     kp_solve_input cluster;          /* nodepools, classes, pods (pending + reschedulable), existing = all state nodes;
                                         host-port tables as in a Solve: an existing node's table holds the ports of all
                                         pods bound to it, the reschedulable pods of candidates included (as `available`
-                                        does); the ports of the pods a probe places are private to that probe */
+                                        does); the ports of the pods a probe places are private to that probe; volume
+                                        tables likewise: a node's table includes the claims of a candidate's
+                                        reschedulable pods, the claims a probe's placements add are private to it */
     const uint8_t* initialized;      /* [n_existing] StateNode.Initialized(); NULL: all initialized */
     int32_t n_pending;               /* provisioner.GetPendingPods, indices into cluster.pods */
     const int32_t* pending;

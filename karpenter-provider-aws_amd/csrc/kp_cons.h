@@ -122,4 +122,12 @@ struct KpCons {
     int32_t pov_cap;
     int32_t* pov_node;          // [FULL workers][pov_cap]
     uint64_t* pov_mask;         // [FULL workers][pov_cap][PW]
+    // volume attach limits (KpDev.VD > 0): a probe that reschedules a pod with a claim on a limited driver is a MUT probe
+    // too.  The claims its placements add are private to it: one overlay entry (node, private counts per limited driver,
+    // shared-claim mask) per such pod it has put on an existing node; a node's claims within the probe are the prepared
+    // base (ex_vcnt0 / ex_vmask0) plus the probe's entries for that node.  vov_cap >= the pods of any probe.
+    int32_t vov_cap;
+    int32_t* vov_node;          // [FULL workers][vov_cap]
+    int32_t* vov_cnt;           // [FULL workers][vov_cap][VD]
+    uint64_t* vov_mask;         // [FULL workers][vov_cap][VW]
 };

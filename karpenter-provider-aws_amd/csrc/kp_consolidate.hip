@@ -341,6 +341,12 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
         uint64_t nc_pm = 0;
         int32_t* const pov_node = (MUT && d.PW > 0) ? k.pov_node + (size_t)wid * k.pov_cap : nullptr;
         uint64_t* const pov_mask = (MUT && d.PW > 0) ? k.pov_mask + (size_t)wid * k.pov_cap * d.PW : nullptr;
+        // volume limits (MUT probes of a pass with d.VD > 0): overlay entries of this probe, and the volume signature of
+        // the pod being placed (0: no claim on a limited driver, no check)
+        int n_vov = 0, cur_vs = 0;
+        int32_t* const vov_node = (MUT && d.VD > 0) ? k.vov_node + (size_t)wid * k.vov_cap : nullptr;
+        int32_t* const vov_cnt = (MUT && d.VD > 0) ? k.vov_cnt + (size_t)wid * k.vov_cap * d.VD : nullptr;
+        uint64_t* const vov_mask = (MUT && d.VD > 0) ? k.vov_mask + (size_t)wid * k.vov_cap * d.VW : nullptr;
         // the ports of class c meet mask m (lane w: word w)
         auto ports_hit = [&](uint64_t m, int c) -> bool {
             return ballot(lane < d.PW && (m & d.cls_ports[(size_t)c * d.PW + (lane < d.PW ? lane : 0)]) != 0) != 0;
@@ -584,6 +590,34 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                 }
                 xw = uni64(xw);
             }
+            // ... and, for a pod with claims on limited drivers, without the nodes whose claim sets (those of the bound
+            // pods plus this probe's overlay entries for the node) would exceed an attach limit with the pod's
+            if (d.VD > 0 && cur_vs) {
+                const int j = w * 64 + lane;
+                bool over = false;
+                if (((xw >> lane) & 1ull) && j < E) {
+                    uint64_t m[KP_MAX_VOL_WORDS];
+#pragma unroll
+                    for (int q = 0; q < KP_MAX_VOL_WORDS; q++)
+                        m[q] = q < d.VW ? (d.ex_vmask0[(size_t)j * d.VW + q] | d.vs_mask[(size_t)cur_vs * d.VW + q]) : 0ull;
+                    for (int i = 0; i < n_vov; i++)
+                        if (ld32(&vov_node[i]) == j) {
+#pragma unroll
+                            for (int q = 0; q < KP_MAX_VOL_WORDS; q++)
+                                if (q < d.VW) m[q] |= ld64u(&vov_mask[(size_t)i * d.VW + q]);
+                        }
+                    for (int kk = 0; kk < d.VD; kk++) {
+                        int used = d.ex_vcnt0[(size_t)kk * E + j] + d.vs_cnt[(size_t)cur_vs * d.VD + kk];
+                        for (int i = 0; i < n_vov; i++)
+                            if (ld32(&vov_node[i]) == j) used += ld32(&vov_cnt[(size_t)i * d.VD + kk]);
+#pragma unroll
+                        for (int q = 0; q < KP_MAX_VOL_WORDS; q++)
+                            if (q < d.VW) used += __popcll(m[q] & d.drv_mask[(size_t)kk * d.VW + q]);
+                        over = over || used > d.ex_vlim[(size_t)kk * E + j];
+                    }
+                }
+                xw = uni64(xw & ~ballot(over));
+            }
             return xw;
         };
         // MUT: ExistingNode.Add's requirement merge of a pod of class c placed on node j (nodeRequirements.Add(pod
@@ -751,7 +785,9 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                             for (int cc = lane; cc < d.C; cc += 64) xtc[cc] = d.XT[(size_t)cc * EW + w] & ~excl[w];
                         cbase = base;
                         cx = xw;
-                        ccls = c;
+                        // the word of a pod with claims on limited drivers is patched for that pod's claims, not for its
+                        // class: the next pod of the class reads the class's word again
+                        ccls = (MUT && mutp && d.VD > 0 && cur_vs) ? -1 : c;
                         cmod = mw;
                         cinit = uni64(initb[w]);
 #pragma unroll
@@ -1018,6 +1054,7 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                 prev_shape = shape;
                 xstart = 0;
             }
+            if (MUT && mutp && d.VD > 0) cur_vs = __builtin_amdgcn_readfirstlane(d.shape_vs[shape]);
             // TOPO: a class counted by some group records each placement; a constrained class's node rejections depend
             // on counts (scan from the first node, no resume)
             uint32_t cflags = 0;
@@ -1069,6 +1106,23 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     n_pov++;
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                // volume limits: the node holds the pod's claims for the rest of this probe (a full slab, which the
+                // sizing at prepare excludes, ends the probe NONE)
+                if (MUT && mutp && d.VD > 0 && cur_vs) {
+                    if (n_vov >= k.vov_cap) {
+                        bad = true;
+                    } else {
+                        if (lane == 0) __hip_atomic_store(&vov_node[n_vov], jf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (lane < d.VD)
+                            __hip_atomic_store(&vov_cnt[(size_t)n_vov * d.VD + lane], d.vs_cnt[(size_t)cur_vs * d.VD + lane],
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (lane < d.VW)
+                            __hip_atomic_store(&vov_mask[(size_t)n_vov * d.VW + lane], d.vs_mask[(size_t)cur_vs * d.VW + lane],
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        n_vov++;
+                        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+                    }
                 }
                 st_placed++;
                 if (!pend) {

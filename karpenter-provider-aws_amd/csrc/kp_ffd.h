@@ -63,6 +63,43 @@ __device__ __forceinline__ void nodeclaim_ports_commit(const KpDev& d, int nc, i
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Volume attach limits (the PORTS instantiations of a solve with d.VD > 0; DESIGN.md §4 "Volume limits")
+// ------------------------------------------------------------------------------------------------
+// ExistingNode.Add's volume check of a pod of volume signature vs (> 0) on node j (one lane per node): for every limited
+// driver the node's private count plus the pod's, plus the shared claims of the driver either holds, stays within the
+// node's limit (INT32_MAX where it has none).  The node's state is written by wave 0's commits alone, which complete
+// before the next scan; a pending same-shape run has nothing here, because volume commits are never deferred.
+__device__ __forceinline__ bool volumes_fit(const KpDev& d, int vs, int j) {
+    uint64_t m[KP_MAX_VOL_WORDS];
+#pragma unroll
+    for (int w = 0; w < KP_MAX_VOL_WORDS; w++)
+        m[w] = w < d.VW ? (__hip_atomic_load(&d.ex_vmask[(size_t)j * d.VW + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) |
+                           d.vs_mask[(size_t)vs * d.VW + w]) : 0ull;
+    bool ok = true;
+    for (int k = 0; k < d.VD; k++) {
+        int used = __hip_atomic_load(&d.ex_vcnt[(size_t)k * d.E + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) +
+                   d.vs_cnt[(size_t)vs * d.VD + k];
+#pragma unroll
+        for (int w = 0; w < KP_MAX_VOL_WORDS; w++)
+            if (w < d.VW) used += __popcll(m[w] & d.drv_mask[(size_t)k * d.VW + w]);
+        ok = ok && used <= d.ex_vlim[(size_t)k * d.E + j];
+    }
+    return ok;
+}
+// One wave: a pod of volume signature vs (> 0) was added to existing node j: the node's claim sets gain the pod's.
+__device__ __forceinline__ void volumes_commit(const KpDev& d, int vs, int j, int lane) {
+    if (lane < d.VD) {
+        const int x = d.vs_cnt[(size_t)vs * d.VD + lane];
+        if (x) atomicAdd(&d.ex_vcnt[(size_t)lane * d.E + j], x);
+    }
+    if (lane < d.VW) {
+        const uint64_t x = d.vs_mask[(size_t)vs * d.VW + lane];
+        if (x) atomicOr((unsigned long long*)&d.ex_vmask[(size_t)j * d.VW + lane], (unsigned long long)x);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");  // complete before the next scan's loads
+}
+
 // ExistingNode.Add's requirement merge of class c into node j (wave 0; only solves whose classes carry
 // NotIn/DoesNotExist keys).  When node j's requirements change, its XT column is recomputed for every class.
 __device__ inline void existing_merge(const KpDev& d, int j, int c, int lane) {
@@ -527,10 +564,16 @@ __device__ __forceinline__ uint64_t held_word(const KpDev& d, int nc, int lane) 
 // cluster"): the first node in scheduling order that is tolerated, Compatible, has headroom and passes
 // Topology.AddRequirements takes the pod; its requirements, the domain counts and its headroom are updated.  Kept out
 // of line: it runs only for clusters, and inlined it would weigh on the topology instantiations' register plan.
+// VOL (the PORTS instantiations): a pod with claims on limited drivers also passes ExistingNode.Add's volume check
+// (volumes_fit) before a node is tried, and the node it lands on gains its claims.
+template <bool VOL = false>
 static __device__ __attribute__((noinline)) int existing_topo_scan(const KpDev* __restrict__ dp, FfdShared& S, int pod, int lane) {
     const KpDev& d = *dp;
     const int K = d.K;
     const int c = S.cur_cls;
+    int vs = 0;
+    if constexpr (VOL)
+        if (d.VD > 0) vs = __builtin_amdgcn_readfirstlane(d.shape_vs[d.pod_shape[pod]]);
     const bool cons = (d.cls_flags[c] & CF_TOPO_CONS) != 0;
     int placed = -1;
     for (int base = 0; base < d.E && placed < 0; base += 64) {
@@ -542,6 +585,8 @@ static __device__ __attribute__((noinline)) int existing_topo_scan(const KpDev* 
             cand = (xw >> (j & 63)) & 1ull;
             for (int ai = 0; ai < d.n_active && cand; ai++)
                 cand = S.pod_req[d.active_axes[ai]] <= ld_req(&d.ex_head[(size_t)ai * d.E + j]);
+            if constexpr (VOL)
+                if (vs && cand) cand = volumes_fit(d, vs, j);
         }
         uint64_t m = ballot(cand);
         while (m) {
@@ -563,6 +608,8 @@ static __device__ __attribute__((noinline)) int existing_topo_scan(const KpDev* 
             const int64_t x = S.pod_req[d.active_axes[lane]];
             if (x) atomicAdd((unsigned long long*)&d.ex_head[(size_t)lane * d.E + placed], (unsigned long long)(-x));
         }
+        if constexpr (VOL)
+            if (vs) volumes_commit(d, vs, placed, lane);
         if (lane == 0) {
             d.pod_result[pod] = -2 - placed;
             d.pod_order[pod] = S.seq++;
@@ -572,6 +619,38 @@ static __device__ __attribute__((noinline)) int existing_topo_scan(const KpDev* 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     return placed;
+}
+
+// Wave 0's existing-node scan for a pod of the current shape (class c, requests S.shape_req) with claims on limited
+// drivers (volume signature vs > 0; the PORTS instantiations): the first node from xstart on that is tolerated and
+// Compatible (XT), has headroom and passes ExistingNode.Add's volume check, with the pod's claims committed to it (the
+// caller places the pod there), or -1.  Out of line for the same reason as
+// existing_topo_scan: the fast loop of the 8-wave PORTS kernels has no registers to spare.
+static __device__ __attribute__((noinline)) int existing_volume_scan(const KpDev* __restrict__ dp, FfdShared& S, int p, int xstart) {
+    const KpDev& d = *dp;
+    // few arguments (each takes a register of the caller at the call): class, signature and lane are derived here
+    const int lane = (int)__lane_id();
+    const int c = __builtin_amdgcn_readfirstlane(d.pod_cls[p]);
+    const int vs = __builtin_amdgcn_readfirstlane(d.shape_vs[d.pod_shape[p]]);
+    for (int base = xstart; base < d.E; base += 64) {
+        const int j = base + lane;
+        bool cand = false;
+        if (j < d.E) {
+            const uint64_t xw = __hip_atomic_load(&d.XT[(size_t)c * d.EW + (j >> 6)], __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+            cand = (xw >> (j & 63)) & 1ull;
+            for (int ai = 0; ai < d.n_active && cand; ai++)
+                cand = S.shape_req[d.active_axes[ai]] <= ld_req(&d.ex_head[(size_t)ai * d.E + j]);
+            if (cand) cand = volumes_fit(d, vs, j);
+        }
+        const uint64_t m = ballot(cand);
+        if (m) {
+            const int jf = base + __ffsll((unsigned long long)m) - 1;
+            volumes_commit(d, vs, jf, lane);  // the node holds the pod's claims from here on
+            return jf;
+        }
+    }
+    return -1;
 }
 
 // PREF: the solve relaxes preferences or runs MIN_VALUES_POLICY=BestEffort; false compiles that code out, so the
@@ -652,7 +731,10 @@ __device__ inline void block_sort_move(FfdShared& S, SortSlice sl, int tid, int 
 // PROF: the diagnostic twin of an entry point (kp_ffd_prof_*.hip; launched when KPSIM_PROFILE or KPSIM_TRACE_POD is
 // set): stage stamps (s_memtime), the cyc_* / n_* / why counters and the trace records.  The production instantiations
 // compile all of it out: those statistics read 0 there, every other one is exact in both.
-// PORTS: the solve carries host ports.  A pod of a port-carrying class (CF_PORTS) conflicts with its own class, so it is
+// PORTS: the solve carries node-side state beyond requests and requirements: host ports (d.PW > 0) and / or volume
+// attach limits (d.VD > 0); each part also sits behind its runtime count.  Volumes touch ExistingNode.Add alone: wave
+// 0's existing-node scan and the block's walk for topology pods test volumes_fit and commit with volumes_commit; the
+// NodeClaim path, quick accepts and batching never see them.  Host ports: a pod of a port-carrying class (CF_PORTS) conflicts with its own class, so it is
 // never quick-accepted or batched: it goes to the block, whose candidate collection leaves out the NodeClaims whose used
 // ports meet the class's; the commits maintain the used-port masks (nc_ports, ex_ports) and the existing nodes' columns.
 // Port-free classes of such a solve take the paths they take anywhere.  PORTS = false compiles all of it out.
@@ -1069,6 +1151,23 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 // pod of a topology class is placed on existing nodes by the block (domain counts, node requirements)
                 if (d.E > 0 && xstart < d.E && !(TOPO_ON && ctopo)) {
                     int jf = -1;
+                    // the shape's volume signature (0: no claim on a limited driver), read where it is needed: not
+                    // another value carried around the loop
+                    const int vs = (PORTS && d.VD > 0) ? __builtin_amdgcn_readfirstlane(d.shape_vs[shape]) : 0;
+                    // a pod with claims on limited drivers: the 8-wave kernels run the scan with ExistingNode.Add's
+                    // volume check out of line (no registers to spare here); it reads the headroom from HBM, so the
+                    // pending run's requests are flushed first (its claims are committed already: volumes_commit is
+                    // never deferred).  The topology kernels (4 waves, twice the registers) test inline below.
+                    bool vscan = false;
+                    if constexpr (PORTS && !TOPO_ON) {
+                        if (vs) {
+                            ex_flush();
+                            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+                            jf = existing_volume_scan(d.self, S, p, xstart);
+                            vscan = true;
+                        }
+                    }
+                    if (!vscan)
                     for (int base = xstart; base < d.E; base += 64) {
                         const int j = base + lane;
                         bool cand = false;
@@ -1084,6 +1183,8 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                                     cand &= pr <= h;
                                 }
                             }
+                            if constexpr (PORTS && TOPO_ON)
+                                if (vs && cand) cand = volumes_fit(d, vs, j);
                         }
                         const uint64_t m = ballot(cand);
                         if (m) {
@@ -1104,6 +1205,8 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                             ex_flush();
                             existing_ports_commit(d, jf, c, lane);
                         }
+                        if constexpr (PORTS && TOPO_ON)
+                            if (vs) volumes_commit(d, vs, jf, lane);  // the node holds the pod's claims from here on
                         if (lane == 0) {
                             d.pod_result[p] = -2 - jf;
                             d.pod_order[p] = seq;
@@ -1578,7 +1681,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             if (S.cls_fill) fill_class_cache<TOPO>(d, S.cur_cls, S.CC, tid, nthr, TOPO ? S.born : 0ull);
             __syncthreads();
             if (wave == 0) {
-                const int placed = existing_topo_scan(d.self, S, pod, lane);
+                const int placed = existing_topo_scan<PORTS>(d.self, S, pod, lane);
                 if (PORTS && placed >= 0) {  // the column the commit recomputed knows no ports; a port pod adds its own
                     if (S.CC.flags & CF_PORTS) existing_ports_commit(d, placed, S.cur_cls, lane);
                     else existing_ports_mask(d, placed, lane);
@@ -2240,7 +2343,7 @@ using namespace KP_WNS;
 
 // A Solve kernel entry point: ffd_solve<RESV, TOPO, PREF, HBM> under its own name, so kernel traces tell the
 // instantiations apart.  A unit compiled with KP_FFD_PROF (kp_ffd_prof_*.hip) defines the diagnostic twin name_prof.
-// KP_FFD_ENTRY_PORTS: a host-port entry point ffd_solve<RESV, TOPO, PREF = true, HBM, PROF, PORTS = true>.  The PREF code is
+// KP_FFD_ENTRY_PORTS: a node-side-state entry point (host ports, volume limits) ffd_solve<RESV, TOPO, PREF = true, HBM, PROF, PORTS = true>.  The PREF code is
 // exact for solves that do not need it (every use is guarded by relax_next / last_ep / best_effort), so the host-port
 // solves share the PREF instantiations instead of doubling their number.
 #ifdef KP_FFD_PROF

@@ -1,4 +1,4 @@
-// kp_ffd_ports.hip — Solve kernel entry points for solves with host ports (ffd_solve PORTS, preference code on): no reserved offerings, no topology groups,
+// kp_ffd_ports.hip — Solve kernel entry points for solves with node-side state: host ports, volume limits (ffd_solve PORTS, preference code on): no reserved offerings, no topology groups,
 // with the slice arrays in LDS or HBM.
 #include "kp_ffd.h"
 

@@ -1,4 +1,4 @@
-// kp_ffd_ports_topo.hip — Solve kernel entry points for solves with host ports (ffd_solve PORTS, preference code on): topology groups, no reserved offerings,
+// kp_ffd_ports_topo.hip — Solve kernel entry points for solves with node-side state: host ports, volume limits (ffd_solve PORTS, preference code on): topology groups, no reserved offerings,
 // with the slice arrays in LDS or HBM.  Built with KP_NWAVES_TOPO waves like the other topology units (kp_ffd_base_topo.hip).
 #ifndef KP_NWAVES_TOPO
 #define KP_NWAVES_TOPO 4  // kp_layout.h

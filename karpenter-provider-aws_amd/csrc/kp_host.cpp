@@ -411,6 +411,10 @@ struct kp_ctx {
     DBuf<uint32_t> d_kflags, d_cls_flags;
     DBuf<uint64_t> d_tol;
     DBuf<uint64_t> d_cls_ports, d_tmpl_ports, d_ex_ports0, d_ex_ports, d_nc_ports;  // host ports (solve_host_ports)
+    // volume attach limits (solve_volumes)
+    DBuf<int32_t> d_shape_vs, d_vs_cnt, d_ex_vlim, d_ex_vcnt0, d_ex_vcnt;
+    DBuf<uint64_t> d_vs_mask, d_drv_mask, d_ex_vmask0, d_ex_vmask;
+    DBuf<uint8_t> d_ex_vover;
     DBuf<ReqHdr> d_ex_hdr0, d_ex_hdr;
     DBuf<uint64_t> d_ex_words0, d_ex_words, d_ex_tol, d_XT;
     DBuf<int64_t> d_ex_avail, d_ex_req, d_ex_head;
@@ -460,7 +464,10 @@ struct kp_ctx {
     DBuf<uint64_t> d_rec_words;
     // MUT probes: per-probe flags (single-node by candidate, multi-node by prefix) and the per-worker node requirement
     // copies of the MUT variant
-    DBuf<int32_t> d_mut_s, d_mut_m, d_ov_slot, d_pov_node;
+    DBuf<int32_t> d_mut_s, d_mut_m, d_ov_slot, d_pov_node, d_vov_node, d_vov_cnt;
+    DBuf<uint64_t> d_vov_mask;
+    std::vector<int32_t> h_pod_vs;           // per pod: volume signature (solve_volumes; empty: no limited driver)
+    std::vector<int64_t> h_vol_enc;          // the prepared solve's volume encoding, serialised (kp_solve_volume_encoding)
     DBuf<uint64_t> d_pov_mask;
     DBuf<ReqHdr> d_ov_hdr;
     DBuf<uint64_t> d_ov_words;
@@ -2007,6 +2014,14 @@ struct SolveEnc {
     // host ports (solve_host_ports): PW mask words over the solve's port-bit dictionary (0: no host ports anywhere)
     int PW = 0, port_bits = 0;
     std::vector<uint64_t> cports, tports, xports;  // [C][PW] classes, [NT][PW] templates' daemonsets, [E][PW] bound pods
+    // volume attach limits (solve_volumes): VD limited drivers, VW mask words over the shared-claim dictionary
+    int VD = 0, VW = 0, vol_bits = 0;
+    std::vector<int32_t> pod_vs;                   // [P] volume signature of the pod (empty: VD == 0)
+    std::vector<int32_t> shape_vs;                 // [shapes] (solve_pods)
+    std::vector<int32_t> vs_cnt, ex_vlim, ex_vcnt; // [signatures][VD], [VD][E], [VD][E]
+    std::vector<uint64_t> vs_mask, drv_mask, ex_vmask;  // [signatures][VW], [VD][VW], [E][VW]
+    std::vector<uint8_t> ex_vover;                 // [E]
+    std::vector<int32_t> vol_drivers;              // [VD] the limited drivers as indices into the input's volume_drivers
 };
 
 static kp_status solve_expand(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
@@ -2495,6 +2510,179 @@ static kp_status solve_host_ports(kp_ctx* ctx, const kp_solve_input* in, SolveEn
     return KP_OK;
 }
 
+// Volume attach limits ([core] scheduling/volumeusage.go and existingnode.go, recalled; DESIGN.md §4 "Volume limits").
+// Drivers without a limit on any node never fail a check and are dropped.  A claim of a limited driver is private when
+// at most one holder can ever meet it, and then it is one unit of an additive count (per pod vcnt[k], per node
+// ex_vcnt[k][j]).  It is shared when two or more pods of the input reference it, or a pod and a node; in a consolidation
+// input a reschedulable pod's own candidate node does not count as "a node" (within a probe the pod and that node never
+// coexist, outside it the pod is not queued).  Each shared claim owns one bit of the input's dictionary; a set union is
+// then a mask OR, and the claims of driver k in it popcount(mask & drv_mask[k]).  A pod's (vcnt[], mask) is interned as
+// its volume signature (0: nothing), which is part of its shape (solve_pods).
+static kp_status solve_volumes(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
+    const int P = in->pods.n_pods, E = se.E, ND = in->n_volume_drivers;
+    if (!in->pod_volume_offsets && !in->existing_volume_offsets && !in->existing_limit_offsets) return KP_OK;
+    if (ND < 0) return fail(ctx, KP_E_INVALID, "volumes: n_volume_drivers");
+    auto dname = [&](int k) {
+        return in->volume_drivers && in->volume_drivers[k] ? std::string(in->volume_drivers[k]) : "#" + std::to_string(k);
+    };
+    std::string err;
+    auto offsets_ok = [&](const int32_t* off, const void* ent, int n) {
+        if (!off) return true;
+        if (off[0] != 0 || (off[n] > 0 && !ent)) return false;
+        for (int i = 0; i < n; i++)
+            if (off[i + 1] < off[i]) return false;
+        return true;
+    };
+    if (!offsets_ok(in->pod_volume_offsets, in->pod_volumes, P) || !offsets_ok(in->existing_volume_offsets, in->existing_volumes, E) ||
+        !offsets_ok(in->existing_limit_offsets, in->existing_limits, E))
+        return fail(ctx, KP_E_INVALID, "volume table offsets");
+    // limits: [E][ND], -1 = none
+    std::vector<int32_t> lim((size_t)std::max(E, 1) * std::max(ND, 1), -1);
+    std::vector<int> kidx(std::max(ND, 1), -1);  // driver -> limited driver
+    if (in->existing_limit_offsets)
+        for (int j = 0; j < E; j++)
+            for (int q = in->existing_limit_offsets[j]; q < in->existing_limit_offsets[j + 1]; q++) {
+                const kp_volume_limit& l = in->existing_limits[q];
+                if (l.driver < 0 || l.driver >= ND) return fail(ctx, KP_E_INVALID, "volume limit: driver index out of range");
+                if (l.limit < 0) return fail(ctx, KP_E_INVALID, "volume limit: negative limit for driver " + dname(l.driver));
+                if (lim[(size_t)j * ND + l.driver] >= 0)
+                    return fail(ctx, KP_E_INVALID, "volume limit: driver " + dname(l.driver) + " listed twice for one node");
+                lim[(size_t)j * ND + l.driver] = l.limit;
+                kidx[l.driver] = 0;
+            }
+    int VD = 0;
+    for (int k = 0; k < ND; k++)
+        if (kidx[k] == 0) kidx[k] = VD++;
+    // rows, validated: a claim id names one claim of one driver
+    std::map<int32_t, int32_t> claim_driver;
+    auto rows_ok = [&](const int32_t* off, const kp_volume* ent, int n) {
+        if (!off) return true;
+        std::vector<std::pair<int32_t, int32_t>> row;
+        for (int i = 0; i < n; i++) {
+            row.clear();
+            for (int q = off[i]; q < off[i + 1]; q++) {
+                const kp_volume& v = ent[q];
+                if (v.driver < 0 || v.driver >= ND) return err = "volume: driver index out of range", false;
+                if (v.id < 0) return err = "volume: negative claim id", false;
+                auto it = claim_driver.emplace(v.id, v.driver).first;
+                if (it->second != v.driver)
+                    return err = "volume: claim " + std::to_string(v.id) + " is listed under drivers " + dname(it->second) + " and " + dname(v.driver), false;
+                row.push_back({v.driver, v.id});
+            }
+            std::sort(row.begin(), row.end());
+            if (std::adjacent_find(row.begin(), row.end()) != row.end()) return err = "volume: a claim is listed twice in one row", false;
+        }
+        return true;
+    };
+    if (!rows_ok(in->pod_volume_offsets, in->pod_volumes, P) || !rows_ok(in->existing_volume_offsets, in->existing_volumes, E))
+        return fail(ctx, KP_E_INVALID, err);
+    if (VD > KP_MAX_VOL_DRIVERS)
+        return fail(ctx, KP_E_UNSUPPORTED, "volume limits: " + std::to_string(VD) + " CSI drivers carry an attach limit in this input; at most " +
+                                           std::to_string(KP_MAX_VOL_DRIVERS) + " are supported");
+    if (VD == 0) return KP_OK;  // no limit anywhere: no check can fail
+    // consolidation: a reschedulable pod's own candidate node (kp_consolidate_prepare's cons_extra)
+    std::vector<int32_t> own(std::max(P, 1), -1);
+    for (const auto& x : ctx->cons_extra)  // {node, pod, candidate}
+        if (x[1] >= 0 && x[1] < P) own[x[1]] = x[0];
+    // holders of every claim of a limited driver: pods referencing it (count, the first), and whether a node that is
+    // not the one referencing pod's own holds it
+    struct Hold {
+        int npods = 0, pod = -1;
+        std::vector<int32_t> nodes;
+    };
+    std::map<int32_t, Hold> holds;
+    auto limited = [&](const kp_volume& v) { return kidx[v.driver] >= 0; };
+    if (in->pod_volume_offsets)
+        for (int p = 0; p < P; p++)
+            for (int q = in->pod_volume_offsets[p]; q < in->pod_volume_offsets[p + 1]; q++)
+                if (limited(in->pod_volumes[q])) {
+                    Hold& h = holds[in->pod_volumes[q].id];
+                    if (h.npods++ == 0) h.pod = p;
+                }
+    if (in->existing_volume_offsets)
+        for (int j = 0; j < E; j++)
+            for (int q = in->existing_volume_offsets[j]; q < in->existing_volume_offsets[j + 1]; q++)
+                if (limited(in->existing_volumes[q])) holds[in->existing_volumes[q].id].nodes.push_back(j);
+    std::map<int32_t, int> bit;  // shared claim -> bit, in claim-id order
+    for (const auto& kv : holds) {
+        const Hold& h = kv.second;
+        bool shared = h.npods >= 2;
+        if (h.npods == 1)
+            for (int32_t j : h.nodes) shared |= j != own[h.pod];
+        if (shared) {
+            const int b = (int)bit.size();
+            bit[kv.first] = b;
+        }
+    }
+    se.vol_bits = (int)bit.size();
+    if (se.vol_bits > KP_MAX_VOL_WORDS * 64)
+        return fail(ctx, KP_E_UNSUPPORTED, "volume limits: the input holds " + std::to_string(se.vol_bits) +
+                                           " shared claims (referenced by two or more pods, or by a pod and a node); at most " +
+                                           std::to_string(KP_MAX_VOL_WORDS * 64) + " are supported");
+    const int VW = (se.vol_bits + 63) / 64, VWa = std::max(VW, 1);
+    se.VD = VD;
+    se.VW = VW;
+    se.vol_drivers.assign(VD, 0);
+    for (int k = 0; k < ND; k++)
+        if (kidx[k] >= 0) se.vol_drivers[kidx[k]] = k;
+    se.drv_mask.assign((size_t)VD * VWa, 0);
+    // one row -> (counts, mask)
+    std::vector<int32_t> cnt(VD);
+    std::vector<uint64_t> msk(VWa);
+    auto encode = [&](const int32_t* off, const kp_volume* ent, int i) {
+        std::fill(cnt.begin(), cnt.end(), 0);
+        std::fill(msk.begin(), msk.end(), 0);
+        if (!off) return;
+        for (int q = off[i]; q < off[i + 1]; q++) {
+            if (!limited(ent[q])) continue;
+            const int k = kidx[ent[q].driver];
+            auto b = bit.find(ent[q].id);
+            if (b == bit.end()) {
+                cnt[k]++;
+            } else {
+                msk[b->second / 64] |= 1ull << (b->second % 64);
+                se.drv_mask[(size_t)k * VWa + b->second / 64] |= 1ull << (b->second % 64);
+            }
+        }
+    };
+    // pods: signatures interned by (counts, mask); signature 0 is "nothing"
+    std::map<std::pair<std::vector<int32_t>, std::vector<uint64_t>>, int32_t> sigs;
+    se.pod_vs.assign(std::max(P, 1), 0);
+    encode(nullptr, nullptr, 0);
+    sigs[{cnt, msk}] = 0;
+    se.vs_cnt.assign(cnt.begin(), cnt.end());
+    se.vs_mask.assign(msk.begin(), msk.end());
+    for (int p = 0; p < P; p++) {
+        encode(in->pod_volume_offsets, in->pod_volumes, p);
+        auto it = sigs.emplace(std::make_pair(cnt, msk), (int32_t)sigs.size());
+        if (it.second) {
+            se.vs_cnt.insert(se.vs_cnt.end(), cnt.begin(), cnt.end());
+            se.vs_mask.insert(se.vs_mask.end(), msk.begin(), msk.end());
+        }
+        se.pod_vs[p] = it.first->second;
+    }
+    // nodes
+    se.ex_vcnt.assign((size_t)VD * std::max(E, 1), 0);
+    se.ex_vlim.assign((size_t)VD * std::max(E, 1), INT32_MAX);
+    se.ex_vmask.assign((size_t)std::max(E, 1) * VWa, 0);
+    se.ex_vover.assign(std::max(E, 1), 0);
+    for (int j = 0; j < E; j++) {
+        encode(in->existing_volume_offsets, in->existing_volumes, j);
+        for (int k = 0; k < VD; k++) se.ex_vcnt[(size_t)k * E + j] = cnt[k];
+        for (int w = 0; w < VW; w++) se.ex_vmask[(size_t)j * VW + w] = msk[w];
+        for (int k = 0; k < ND; k++)
+            if (kidx[k] >= 0 && lim[(size_t)j * ND + k] >= 0) se.ex_vlim[(size_t)kidx[k] * E + j] = lim[(size_t)j * ND + k];
+    }
+    // over a limit at prepare (the masks are complete only now): the node refuses every pod
+    for (int j = 0; j < E; j++)
+        for (int k = 0; k < VD; k++) {
+            int64_t used = se.ex_vcnt[(size_t)k * E + j];
+            for (int w = 0; w < VW; w++) used += __builtin_popcountll(se.ex_vmask[(size_t)j * VW + w] & se.drv_mask[(size_t)k * VWa + w]);
+            if (used > se.ex_vlim[(size_t)k * E + j]) se.ex_vover[j] = 1;
+        }
+    return KP_OK;
+}
+
 static kp_status solve_pods(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se) {
     const int R = ctx->R, P = in->pods.n_pods, C = in->n_classes, NT = se.NT;
     // ---- pods ----
@@ -2519,11 +2707,15 @@ static kp_status solve_pods(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se)
     for (int j = 0; j < NT; j++)
         for (int r = 0; r < R; r++)
             if (se.daemon[(size_t)j * R + r] != 0) active[r] = 1;
-    // shapes: (class, requests) interned in an open-addressing table of shape ids; a shape's requests point at the
-    // pinned row of its first pod (relaxation stages share the row of the shape they relax)
+    // shapes: (class, requests, volume signature) interned in an open-addressing table of shape ids; a shape's requests
+    // point at the pinned row of its first pod (relaxation stages share the row of the shape they relax).  The volume
+    // signature (solve_volumes; 0 without limited volumes) makes pods with different volume demand different shapes: a
+    // node's claim sets only grow within a Solve, so a shape's rejection by a node stays permanent.
+    const int32_t* const pvs = se.VD > 0 ? se.pod_vs.data() : nullptr;
     struct ShapeRec {
         int cls;
         const int64_t* req;
+        int vs;
     };
     std::vector<ShapeRec> shapes;
     std::vector<int32_t>& stab = ctx->h_shape_tab;
@@ -2531,29 +2723,29 @@ static kp_status solve_pods(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se)
     while (SHT < (size_t)P * 2) SHT <<= 1;
     if (stab.size() < SHT) stab.resize(SHT);
     std::fill(stab.begin(), stab.begin() + SHT, -1);
-    auto shape_hash = [&](int cl, const int64_t* rq) {
-        uint64_t h = (uint64_t)(uint32_t)cl * 0x9E3779B97F4A7C15ull;
+    auto shape_hash = [&](int cl, const int64_t* rq, int vs) {
+        uint64_t h = ((uint64_t)(uint32_t)cl | ((uint64_t)(uint32_t)vs << 32)) * 0x9E3779B97F4A7C15ull;
         for (int r = 0; r < R; r++) h = (h ^ (uint64_t)rq[r]) * 0xBF58476D1CE4E5B9ull + 0x94D049BB133111EBull;
         return (size_t)(h ^ (h >> 31));
     };
-    auto shape_id = [&](int cl, const int64_t* rq) -> int {
+    auto shape_id = [&](int cl, const int64_t* rq, int vs) -> int {
         if (shapes.size() * 2 >= SHT) {  // keep the load ≤ 1/2 (relaxation stages can add shapes beyond P)
             SHT <<= 1;
             stab.assign(SHT, -1);
             for (size_t i = 0; i < shapes.size(); i++) {
-                size_t h = shape_hash(shapes[i].cls, shapes[i].req) & (SHT - 1);
+                size_t h = shape_hash(shapes[i].cls, shapes[i].req, shapes[i].vs) & (SHT - 1);
                 while (stab[h] >= 0) h = (h + 1) & (SHT - 1);
                 stab[h] = (int32_t)i;
             }
         }
-        for (size_t h = shape_hash(cl, rq) & (SHT - 1);; h = (h + 1) & (SHT - 1)) {
+        for (size_t h = shape_hash(cl, rq, vs) & (SHT - 1);; h = (h + 1) & (SHT - 1)) {
             const int id = stab[h];
             if (id < 0) {
                 stab[h] = (int32_t)shapes.size();
-                shapes.push_back({cl, rq});
+                shapes.push_back({cl, rq, vs});
                 return (int)shapes.size() - 1;
             }
-            if (shapes[id].cls == cl && memcmp(shapes[id].req, rq, sizeof(int64_t) * R) == 0) return id;
+            if (shapes[id].cls == cl && shapes[id].vs == vs && memcmp(shapes[id].req, rq, sizeof(int64_t) * R) == 0) return id;
         }
     };
     // NewQueue's UID tie-break enters as the UID's first 8 bytes; distinct UIDs sharing them are detected with an
@@ -2595,10 +2787,11 @@ static kp_status solve_pods(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se)
             }
             // shapes are numbered in order of first appearance; a pod with the previous pod's class and requests (the
             // pods of one Deployment, typically) reuses its shape without a lookup
-            if (p > 0 && cl == pcls[p - 1] && memcmp(dst, dst - R, sizeof(int64_t) * R) == 0) {
+            const int vs = pvs ? pvs[p] : 0;
+            if (p > 0 && cl == pcls[p - 1] && (!pvs || vs == pvs[p - 1]) && memcmp(dst, dst - R, sizeof(int64_t) * R) == 0) {
                 pshape[p] = prev_shape;
             } else {
-                pshape[p] = prev_shape = shape_id(cl, dst);
+                pshape[p] = prev_shape = shape_id(cl, dst, vs);
             }
         }
     };
@@ -2661,8 +2854,12 @@ static kp_status solve_pods(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& se)
     if (!ctx->pref.relax_next.empty()) {
         for (size_t sid = 0; sid < shapes.size(); sid++) {
             const int nx = ctx->pref.relax_next[shapes[sid].cls];
-            se.shape_next.push_back(nx >= 0 ? shape_id(nx, shapes[sid].req) : -1);
+            se.shape_next.push_back(nx >= 0 ? shape_id(nx, shapes[sid].req, shapes[sid].vs) : -1);
         }
+    }
+    if (pvs) {
+        se.shape_vs.resize(shapes.size());
+        for (size_t sid = 0; sid < shapes.size(); sid++) se.shape_vs[sid] = shapes[sid].vs;
     }
     KpDev& d = ctx->dev;
     d = KpDev{};
@@ -2715,6 +2912,19 @@ static kp_status solve_upload(kp_ctx* ctx, const kp_solve_input* in, SolveEnc& s
         HIPCHK(c->d_tmpl_ports.upload(se.tports, s));
         HIPCHK(c->d_ex_ports0.upload(se.xports, s));
         HIPCHK(c->d_ex_ports.ensure(se.xports.size()));
+    }
+    if (se.VD > 0) {
+        if (se.shape_vs.empty()) se.shape_vs.push_back(0);
+        HIPCHK(c->d_shape_vs.upload(se.shape_vs, s));
+        HIPCHK(c->d_vs_cnt.upload(se.vs_cnt, s));
+        HIPCHK(c->d_vs_mask.upload(se.vs_mask, s));
+        HIPCHK(c->d_drv_mask.upload(se.drv_mask, s));
+        HIPCHK(c->d_ex_vlim.upload(se.ex_vlim, s));
+        HIPCHK(c->d_ex_vcnt0.upload(se.ex_vcnt, s));
+        HIPCHK(c->d_ex_vcnt.ensure(se.ex_vcnt.size()));
+        HIPCHK(c->d_ex_vmask0.upload(se.ex_vmask, s));
+        HIPCHK(c->d_ex_vmask.ensure(se.ex_vmask.size()));
+        HIPCHK(c->d_ex_vover.upload(se.ex_vover, s));
     }
     HIPCHK(c->d_daemon.upload(se.daemon, s));
     HIPCHK(c->d_limit_set.upload(se.limit_set, s));
@@ -3196,6 +3406,12 @@ static kp_status solve_fill_dev(kp_ctx* ctx, const kp_solve_input* in, SolveEnc&
     if (se.PW > 0) {
         DEV(cls_ports); DEV(tmpl_ports); DEV(ex_ports0); DEV(ex_ports); DEV(nc_ports);
     }
+    d.VD = se.VD;  // volume attach limits
+    d.VW = se.VW;
+    if (se.VD > 0) {
+        DEV(shape_vs); DEV(vs_cnt); DEV(vs_mask); DEV(drv_mask); DEV(ex_vlim); DEV(ex_vcnt0); DEV(ex_vcnt); DEV(ex_vmask0);
+        DEV(ex_vmask); DEV(ex_vover);
+    }
     HIPCHK(c->d_tmpl_lmask.ensure((size_t)std::max(1, d.NT) * std::max(1, d.TW)));
     DEV(tmpl_lmask); DEV(min_keys);
     d.E = E;
@@ -3332,6 +3548,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     STAGE(solve_template_tables);
     STAGE(solve_existing_digests);
     STAGE(solve_host_ports);
+    STAGE(solve_volumes);
     PREP_MARK(2);
     STAGE(solve_pods);  // PREP_MARK(3) sits inside, between the pod passes and shape_next.  Resets ctx->dev and sets its
                         // active axes; solve_topology_tables adds snap_rows, born0 and HN; solve_fill_dev the rest
@@ -3349,6 +3566,26 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     c->K = se.K;
     c->DW = se.DW;
     c->M = se.M;
+    c->h_pod_vs = se.VD > 0 ? se.pod_vs : std::vector<int32_t>();
+    {  // kp_solve_volume_encoding's record: header, then the tables in the order kpsim.h lists
+        std::vector<int64_t>& v = c->h_vol_enc;
+        const int VD = se.VD, VW = se.VW, VWa = std::max(VW, 1), P = in->pods.n_pods, E = se.E;
+        const int NS = VD > 0 ? (int)se.vs_cnt.size() / VD : 0;
+        v = {VD, VW, se.vol_bits, NS, VD > 0 ? P : 0, VD > 0 ? E : 0};
+        if (VD > 0) {
+            for (int k = 0; k < VD; k++) v.push_back(se.vol_drivers[k]);
+            for (int p = 0; p < P; p++) v.push_back(se.pod_vs[p]);
+            for (int i = 0; i < NS * VD; i++) v.push_back(se.vs_cnt[i]);
+            for (int s = 0; s < NS; s++)
+                for (int w = 0; w < VW; w++) v.push_back((int64_t)se.vs_mask[(size_t)s * VWa + w]);
+            for (int k = 0; k < VD; k++)
+                for (int w = 0; w < VW; w++) v.push_back((int64_t)se.drv_mask[(size_t)k * VWa + w]);
+            for (int i = 0; i < VD * E; i++) v.push_back(se.ex_vcnt[i]);
+            for (int i = 0; i < VD * E; i++) v.push_back(se.ex_vlim[i]);
+            for (int i = 0; i < E * VW; i++) v.push_back((int64_t)se.ex_vmask[i]);
+            for (int j = 0; j < E; j++) v.push_back(se.ex_vover[j]);
+        }
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->ns_prep = ns_since(t0);
     c->prepared = true;
@@ -3357,6 +3594,16 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     return fail(ctx, KP_E_INVALID, e.what());
 }
 #undef STAGE
+
+// The volume encoding of the prepared solve or consolidation pass (solve_volumes), for audits and tests.
+extern "C" kp_status kp_solve_volume_encoding(kp_ctx* ctx, int64_t* buf, int64_t cap, int64_t* needed) {
+    if (!ctx || !needed) return KP_E_INVALID;
+    if (!ctx->prepared && !ctx->cons_prepared) return fail(ctx, KP_E_STATE, "kp_solve_volume_encoding before a prepare");
+    *needed = (int64_t)ctx->h_vol_enc.size();
+    if (!buf || cap < *needed) return KP_E_BUFFER;
+    std::copy(ctx->h_vol_enc.begin(), ctx->h_vol_enc.end(), buf);
+    return KP_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // solve: execute (device only)
@@ -3736,7 +3983,8 @@ static kp_status cons_mutators(kp_ctx* ctx, const kp_consolidate_input* in) {
     for (int i = 0; i < C0; i++)
         for (int s = i; s >= 0 && !chain[i]; s = ctx->pref.relax_next.empty() ? -1 : ctx->pref.relax_next[s])
             if (s < (int)ctx->cons_mutcls.size() && ctx->cons_mutcls[s]) chain[i] = 1;
-    auto pod_mut = [&](int p) { return chain[cl.pods.class_id[p]] != 0; };
+    // ... or holds a claim on a limited driver (per pod: the node then holds it for the rest of the probe)
+    auto pod_mut = [&](int p) { return chain[cl.pods.class_id[p]] != 0 || (!ctx->h_pod_vs.empty() && ctx->h_pod_vs[p] != 0); };
     bool pend_mut = false;
     for (int i = 0; i < in->n_pending; i++) pend_mut = pend_mut || pod_mut(in->pending[i]);
     const int mx = ctx->cons_max_candidates;
@@ -4042,6 +4290,15 @@ static kp_status cons_run(kp_ctx* ctx, int m0, int m1, int s0, int s1, kp_probe_
             HIPCHK(c->d_pov_mask.ensure((size_t)fw * k.pov_cap * d.PW));
             k.pov_node = c->d_pov_node.p;
             k.pov_mask = c->d_pov_mask.p;
+        }
+        k.vov_cap = k.pov_cap;  // volume limits: likewise
+        if (d.VD > 0) {
+            HIPCHK(c->d_vov_node.ensure((size_t)fw * k.vov_cap));
+            HIPCHK(c->d_vov_cnt.ensure((size_t)fw * k.vov_cap * d.VD));
+            HIPCHK(c->d_vov_mask.ensure((size_t)fw * k.vov_cap * std::max(d.VW, 1)));
+            k.vov_node = c->d_vov_node.p;
+            k.vov_cnt = c->d_vov_cnt.p;
+            k.vov_mask = c->d_vov_mask.p;
         }
     }
     k.pbits = c->d_pbits.p;

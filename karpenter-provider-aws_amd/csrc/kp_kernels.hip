@@ -53,8 +53,13 @@ __global__ __launch_bounds__(256) void existing_init_kernel(KpDev d) {
         for (int ai = 0; ai < d.n_active; ai++) act |= act_axis(d, ai) == r;
         if (av < 0 || (!act && rq > av)) ok = false;
     }
+    // volume limits: a node over an attach limit refuses every pod (ExceedsLimits runs over the union's drivers), and
+    // no Add takes a node over a limit, so this is static; every derivation of a class x node bit reads ex_static
+    if (d.VD > 0 && d.ex_vover[j]) ok = false;
     d.ex_static[j] = ok ? 1 : 0;
     for (int pw = 0; pw < d.PW; pw++) d.ex_ports[(size_t)j * d.PW + pw] = d.ex_ports0[(size_t)j * d.PW + pw];  // bound pods' host ports
+    for (int k = 0; k < d.VD; k++) d.ex_vcnt[(size_t)k * d.E + j] = d.ex_vcnt0[(size_t)k * d.E + j];  // ... and volumes
+    for (int w = 0; w < (d.VD > 0 ? d.VW : 0); w++) d.ex_vmask[(size_t)j * d.VW + w] = d.ex_vmask0[(size_t)j * d.VW + w];
     for (int ai = 0; ai < d.n_active; ai++) {
         const int r = act_axis(d, ai);
         d.ex_head[(size_t)ai * d.E + j] = d.ex_avail[(size_t)j * d.R + r] - d.ex_req[(size_t)j * d.R + r];
@@ -144,7 +149,7 @@ KP_FFD_DECL(ffd_pref_hbm_kernel)
 KP_FFD_DECL(ffd_pref_topo_hbm_kernel)
 KP_FFD_DECL(ffd_pref_resv_hbm_kernel)
 KP_FFD_DECL(ffd_pref_resv_topo_hbm_kernel)
-// host ports (ffd_solve PORTS, with PREF on): kp_ffd_ports{,_resv}{,_topo}.hip
+// node-side state: host ports, volume limits (ffd_solve PORTS, with PREF on): kp_ffd_ports{,_resv}{,_topo}.hip
 KP_FFD_DECL(ffd_ports_kernel)
 KP_FFD_DECL(ffd_ports_topo_kernel)
 KP_FFD_DECL(ffd_ports_resv_kernel)
@@ -163,7 +168,7 @@ typedef void (*FfdKernel)(KpDev);
      ffd_pref_hbm_kernel##sfx, ffd_pref_topo_hbm_kernel##sfx, ffd_pref_resv_hbm_kernel##sfx, ffd_pref_resv_topo_hbm_kernel##sfx}
 static const FfdKernel kFfdKernels[2][16] = {KP_FFD_ROW(), KP_FFD_ROW(_prof)};
 #undef KP_FFD_ROW
-// solves with host ports: [diagnostic twin][HBM * 4 + RESV * 2 + TOPO]
+// solves with host ports or volume limits: [diagnostic twin][HBM * 4 + RESV * 2 + TOPO]
 #define KP_FFD_PORTS_ROW(sfx)                                                                                            \
     {ffd_ports_kernel##sfx,     ffd_ports_topo_kernel##sfx,     ffd_ports_resv_kernel##sfx,     ffd_ports_resv_topo_kernel##sfx, \
      ffd_ports_hbm_kernel##sfx, ffd_ports_topo_hbm_kernel##sfx, ffd_ports_resv_hbm_kernel##sfx, ffd_ports_resv_topo_hbm_kernel##sfx}
@@ -494,8 +499,9 @@ hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s) {
     const bool pref = d.relax_next || d.best_effort;
     // KPSIM_PROFILE / KPSIM_TRACE_POD: the diagnostic twin (the production kernels carry no stamps, n_* counters or trace)
     const int twin = (d.profile || d.trace) ? 1 : 0;
-    // a solve with host ports (PW > 0) runs its own instantiations; every other solve the entry point it always had
-    const FfdKernel k = d.PW > 0 ? kFfdPortsKernels[twin][(d.slice_hbm ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)]
+    // a solve with node-side state beyond requests (host ports, PW > 0; volume limits, VD > 0) runs the PORTS
+    // instantiations; every other solve the entry point it always had
+    const FfdKernel k = (d.PW > 0 || d.VD > 0) ? kFfdPortsKernels[twin][(d.slice_hbm ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)]
                                  : kFfdKernels[twin][(d.slice_hbm ? 8 : 0) + (pref ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)];
     hipLaunchKernelGGL(k, g, b, bytes, s, d);
     return hipGetLastError();

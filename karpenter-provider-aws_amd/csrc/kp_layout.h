@@ -52,7 +52,9 @@
 #define KP_CC_TC 16                  // constraining groups a ClassCache holds (the rest are read from cls_tc)
 #define KP_MAX_TOPO_KEYS 8           // distinct value-keyed topology keys among a class's constraining groups
 #define KP_MAX_PORT_WORDS 4          // u64 words of a host-port mask: the port-bit dictionary of one solve (256 bits)
-#define KP_TRACE_N 16384             // diagnostics ring (KPSIM_TRACE_*)           // topology groups recording one pod class's placements
+#define KP_MAX_VOL_DRIVERS 8         // CSI drivers with an attach limit on some node of one input
+#define KP_MAX_VOL_WORDS 4           // u64 words of a shared-claim mask: the shared-claim dictionary of one input (256 bits)
+#define KP_TRACE_N 16384            // diagnostics ring (KPSIM_TRACE_*)           // topology groups recording one pod class's placements
 
 // cls_flags bits
 #define CF_OFFERING 1u               // constrains an offering key
@@ -341,6 +343,24 @@ struct KpDev {
     const uint64_t* ex_ports0;       // [E][PW] ports of the pods bound to the node
     uint64_t* ex_ports;              // [E][PW] working copy: + the port pods this solve placed on the node
     uint64_t* nc_ports;              // [NCcap][PW] used ports of the in-flight NodeClaims
+
+    // ---------------- volume attach limits ([core] scheduling/volumeusage.go; DESIGN.md §4 "Volume limits") ----------
+    // kp_host.cpp solve_volumes.  A claim only one holder can ever meet is private and enters additive counts; a shared
+    // claim owns one bit of the solve's shared-claim dictionary.  With a pod of volume signature s on node j, driver k
+    // holds  ex_vcnt[k][j] + vs_cnt[s][k] + popcount((ex_vmask[j] | vs_mask[s]) & drv_mask[k])  claims, and
+    // ExistingNode.Add fails when that exceeds ex_vlim[k][j] for some k.  VD == 0: no limited driver in the input (the
+    // other fields are unset).  Read by the node-side-state (PORTS) entry points and the MUT probes alone.
+    int32_t VD, VW;                  // limited drivers (<= KP_MAX_VOL_DRIVERS), shared mask words (<= KP_MAX_VOL_WORDS, may be 0)
+    const int32_t* shape_vs;         // [shapes] volume signature of the shape's pods (0: no claim on a limited driver)
+    const int32_t* vs_cnt;           // [signatures][VD] private claims per limited driver
+    const uint64_t* vs_mask;         // [signatures][VW] shared claims
+    const uint64_t* drv_mask;        // [VD][VW] the shared claims of each limited driver
+    const int32_t* ex_vlim;          // [VD][E] attach limit (INT32_MAX: the node has none for the driver)
+    const int32_t* ex_vcnt0;         // [VD][E] private claims of the pods bound to the node
+    int32_t* ex_vcnt;                // [VD][E] working copy: + the pods this solve placed on the node
+    const uint64_t* ex_vmask0;       // [E][VW] shared claims the node mounts
+    uint64_t* ex_vmask;              // [E][VW] working copy
+    const uint8_t* ex_vover;         // [E] the node is over a limit at prepare: ExistingNode.Add fails for every pod
 };
 
 // stats slots

@@ -110,7 +110,18 @@ class kp_host_port(C.Structure):
     _fields_ = [("ip", C.c_char_p), ("protocol", C.c_int32), ("port", C.c_int32)]
 
 
+class kp_volume(C.Structure):
+    _fields_ = [("driver", C.c_int32), ("id", C.c_int32)]
+
+
+class kp_volume_limit(C.Structure):
+    _fields_ = [("driver", C.c_int32), ("limit", C.c_int32)]
+
+
 class kp_solve_input(C.Structure):
+    """The C struct's fields up to the host-port tables.  NOT the whole struct: the volume tables follow in
+    kp_solve_input_full, which is what every call into the library takes (native.py declares POINTER(kp_solve_input_full),
+    so ctypes refuses an instance of this shorter class; never pass one through a cast)."""
     _fields_ = [("n_nodepools", C.c_int32), ("nodepools", C.POINTER(kp_nodepool)),
                 ("n_classes", C.c_int32), ("classes", C.POINTER(kp_pod_class)),
                 ("pods", kp_pods_view),
@@ -120,6 +131,16 @@ class kp_solve_input(C.Structure):
                 ("class_port_offsets", c_int32_p), ("class_ports", C.POINTER(kp_host_port)),
                 ("nodepool_port_offsets", c_int32_p), ("nodepool_ports", C.POINTER(kp_host_port)),
                 ("existing_port_offsets", c_int32_p), ("existing_ports", C.POINTER(kp_host_port))]
+
+
+class kp_solve_input_full(kp_solve_input):
+    """The whole C struct kp_solve_input: the mirror above (its fields up to the host-port tables, at the offsets they
+    always had) followed by the volume tables (ctypes lays a subclass's fields out behind its base's).  Every view
+    handed to the library is one of these; a pointer to it is accepted wherever POINTER(kp_solve_input) is declared."""
+    _fields_ = [("n_volume_drivers", C.c_int32), ("volume_drivers", c_char_pp),
+                ("pod_volume_offsets", c_int32_p), ("pod_volumes", C.POINTER(kp_volume)),
+                ("existing_volume_offsets", c_int32_p), ("existing_volumes", C.POINTER(kp_volume)),
+                ("existing_limit_offsets", c_int32_p), ("existing_limits", C.POINTER(kp_volume_limit))]
 
 
 class kp_solve_stats(C.Structure):
@@ -149,7 +170,7 @@ class kp_candidate(C.Structure):
 
 
 class kp_consolidate_input(C.Structure):
-    _fields_ = [("cluster", kp_solve_input), ("initialized", c_uint8_p), ("n_pending", C.c_int32),
+    _fields_ = [("cluster", kp_solve_input_full), ("initialized", c_uint8_p), ("n_pending", C.c_int32),
                 ("pending", c_int32_p), ("n_candidates", C.c_int32), ("candidates", C.POINTER(kp_candidate)),
                 ("mode", C.c_int32), ("max_candidates", C.c_int32), ("probe_begin", C.c_int32),
                 ("probe_end", C.c_int32), ("spot_to_spot", C.c_int32)]
@@ -333,3 +354,39 @@ def host_port_rows(offsets, entries, n):
         return [[] for _ in range(n)]
     return [[((entries[i].ip or b"").decode(), int(entries[i].protocol), int(entries[i].port))
              for i in range(offsets[r], offsets[r + 1])] for r in range(n)]
+
+
+def pair_csr(keep, rows, struct, fields):
+    """rows: one list of int pairs per pod / node -> (offsets pointer, entries pointer), a CSR side table of
+    kp_solve_input over a two-int32 struct (kp_volume, kp_volume_limit); (None, None) when every row is empty."""
+    rows = [list(r) for r in rows]
+    if not any(rows):
+        return None, None
+    off = np.zeros(len(rows) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(r) for r in rows])
+    arr = (struct * max(1, int(off[-1])))()
+    i = 0
+    for r in rows:
+        for a, b in r:
+            setattr(arr[i], fields[0], int(a))
+            setattr(arr[i], fields[1], int(b))
+            i += 1
+    keep.hold(arr)
+    return keep.ptr(off, np.int32, C.c_int32), C.cast(arr, C.POINTER(struct))
+
+
+def volume_tables(keep, view, pod_volumes, node_volumes, node_limits):
+    """Fill kp_solve_input's volume fields.  pod_volumes / node_volumes: per pod / node, a list of (driver name, claim
+    key); node_limits: per node, {driver name: attach limit}.  Driver names and claim keys are numbered densely in order
+    of first appearance (equal keys: the same claim)."""
+    drivers, claims = {}, {}
+
+    def ids(rows):
+        return [[(drivers.setdefault(d, len(drivers)), claims.setdefault(c, len(claims))) for d, c in r] for r in rows]
+    pv, xv = ids(pod_volumes), ids(node_volumes)
+    xl = [[(drivers.setdefault(d, len(drivers)), n) for d, n in sorted(lim.items())] for lim in node_limits]
+    view.n_volume_drivers = len(drivers)
+    view.volume_drivers = keep.cstrs(list(drivers))
+    view.pod_volume_offsets, view.pod_volumes = pair_csr(keep, pv, kp_volume, ("driver", "id"))
+    view.existing_volume_offsets, view.existing_volumes = pair_csr(keep, xv, kp_volume, ("driver", "id"))
+    view.existing_limit_offsets, view.existing_limits = pair_csr(keep, xl, kp_volume_limit, ("driver", "limit"))

@@ -167,6 +167,9 @@ class Pods:
     requests: np.ndarray      # [P, R] int64 milli (incl. pods = 1000)
     creation_ns: np.ndarray   # [P] int64
     uids: List[str]
+    # per pod, its volumes on CSI drivers: (driver name, claim key) pairs (kpsim.h kp_volume); claim key = the PVC's
+    # namespace/name, or pod-name-volume for a generic ephemeral volume; equal keys are one claim.  None: no volumes
+    volumes: Optional[List[List[Tuple[str, str]]]] = None
 
     @property
     def n(self):
@@ -181,6 +184,8 @@ class ExistingNode:
     requests: Optional[np.ndarray] = None
     taints: List[Taint] = field(default_factory=list)
     host_ports: List[HostPort] = field(default_factory=list)   # host ports of every pod bound to the node
+    volumes: List[Tuple[str, str]] = field(default_factory=list)  # (driver, claim key) of every pod bound to the node
+    volume_limits: Dict[str, int] = field(default_factory=dict)   # driver -> CSINode Allocatable.Count; absent: no limit
 
 
 @dataclass
@@ -346,7 +351,7 @@ class SolveInputView:
             if e.requests is not None:
                 ex[i].requests = k.ptr(e.requests, np.int64, C.c_int64)
         k.hold(ex)
-        v = self.view = abi.kp_solve_input()
+        v = self.view = abi.kp_solve_input_full()
         v.n_nodepools = len(prob.nodepools)
         v.nodepools = nps
         v.n_classes = len(prob.classes)
@@ -369,6 +374,8 @@ class SolveInputView:
         v.class_port_offsets, v.class_ports = abi.host_port_csr(k, [pc.host_ports for pc in prob.classes])
         v.nodepool_port_offsets, v.nodepool_ports = abi.host_port_csr(k, [n.daemon_host_ports for n in prob.nodepools])
         v.existing_port_offsets, v.existing_ports = abi.host_port_csr(k, [e.host_ports for e in prob.existing])
+        abi.volume_tables(k, v, p.volumes if p.volumes is not None else [[] for _ in range(p.n)],
+                          [e.volumes for e in prob.existing], [e.volume_limits for e in prob.existing])
 
 
 @dataclass

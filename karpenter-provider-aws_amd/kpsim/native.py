@@ -13,7 +13,7 @@ EXPORTS = [
     "kp_result_nodeclaim_requirements", "kp_last_kernel_times", "kp_consolidate_probe_count", "kp_consolidate",
     "kp_consolidate_stats", "kp_consolidate_prepare", "kp_consolidate_execute", "kp_launch_select", "kp_launch_stats",
     "kp_nodeclaim_labels", "kp_catalog_build", "kp_catalog_get_view", "kp_catalog_overhead", "kp_catalog_resource_name",
-    "kp_catalog_free", "kp_consolidate_command", "kp_consolidate_replacement",
+    "kp_catalog_free", "kp_consolidate_command", "kp_consolidate_replacement", "kp_solve_volume_encoding",
 ]
 
 _lib = None
@@ -42,8 +42,11 @@ def load():
     L.kp_catalog_upload.argtypes = [C.c_void_p, C.POINTER(abi.kp_catalog_view), C.c_uint64]
     L.kp_catalog_patch_avail.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_uint64]
     L.kp_catalog_patch_price.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_uint64]
-    L.kp_solve.argtypes = [C.c_void_p, C.POINTER(abi.kp_solve_input), C.POINTER(abi.kp_solve_output)]
-    L.kp_solve_prepare.argtypes = [C.c_void_p, C.POINTER(abi.kp_solve_input)]
+    # the whole C struct: ctypes then refuses the shorter mirror abi.kp_solve_input, which ends before the volume tables
+    L.kp_solve.argtypes = [C.c_void_p, C.POINTER(abi.kp_solve_input_full), C.POINTER(abi.kp_solve_output)]
+    L.kp_solve_prepare.argtypes = [C.c_void_p, C.POINTER(abi.kp_solve_input_full)]
+    if hasattr(L, "kp_solve_volume_encoding"):  # (absent from older libraries, A/B only)
+        L.kp_solve_volume_encoding.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     L.kp_solve_execute.argtypes = [C.c_void_p]
     L.kp_solve_fetch.argtypes = [C.c_void_p, C.POINTER(abi.kp_solve_output)]
     L.kp_result_nodeclaim_requirements.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
@@ -156,6 +159,27 @@ class Context:
 
     def execute(self):
         self.check(self.L.kp_solve_execute(self.h), "kp_solve_execute")
+
+    def volume_encoding(self):
+        """kp_solve_volume_encoding of the prepared Solve or consolidation pass, as a dict of numpy arrays."""
+        import numpy as np
+        need = C.c_int64(0)
+        st = self.L.kp_solve_volume_encoding(self.h, None, 0, C.byref(need))
+        if st not in (abi.KP_OK, abi.KP_E_BUFFER):
+            self.check(st, "kp_solve_volume_encoding")
+        buf = np.zeros(max(1, need.value), np.int64)
+        self.check(self.L.kp_solve_volume_encoding(self.h, buf.ctypes.data_as(C.POINTER(C.c_int64)), buf.size,
+                                                   C.byref(need)), "kp_solve_volume_encoding")
+        VD, VW, bits, NS, P, E = (int(x) for x in buf[:6])
+        out, pos = {"VD": VD, "VW": VW, "bits": bits, "NS": NS}, 6
+        for name, shape in (("limited_driver", (VD,)), ("pod_signature", (P,)), ("signature_count", (NS, VD)),
+                            ("signature_mask", (NS, VW)), ("driver_mask", (VD, VW)), ("node_count", (VD, E)),
+                            ("node_limit", (VD, E)), ("node_mask", (E, VW)), ("node_over_limit", (E,))):
+            n = int(np.prod(shape))
+            a = buf[pos:pos + n].reshape(shape) if VD > 0 else np.zeros((0,) * len(shape), np.int64)
+            out[name] = a.view(np.uint64) if name.endswith("mask") else a
+            pos += n if VD > 0 else 0
+        return out
 
     def fetch(self, out_buffers):
         self.check(self.L.kp_solve_fetch(self.h, C.byref(out_buffers.view)), "kp_solve_fetch")

@@ -4,6 +4,8 @@ Mirrors [core] pkg/controllers/provisioning/scheduling/scheduler.go — NewSched
 instanceTypes, ...) then Solve(pods) -> Results{NewNodeClaims, ExistingNodes, PodErrors} — followed by
 Results.TruncateInstanceTypes(maxInstanceTypes=60) as the provisioner does (instance.go:62,293).  The
 instance-type catalog is what CloudProvider.GetInstanceTypes returns (pkg/cloudprovider/cloudprovider.go:181).
+Volume attach limits travel with the Problem: Pods.volumes, ExistingNode.volumes and ExistingNode.volume_limits
+(model.SolveInputView marshals them into kp_solve_input's three volume tables).
 """
 from dataclasses import dataclass
 from typing import Dict, List, Optional

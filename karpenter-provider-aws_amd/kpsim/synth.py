@@ -190,7 +190,8 @@ def subsample(prob: Problem, n_pods: int, seed=SEED) -> Problem:
     """A bounded sample of a problem's pods (same catalog/pools/classes), for oracle-sized runs."""
     p = prob.pods
     idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(p.n, size=min(n_pods, p.n), replace=False))
-    pods = Pods(p.class_id[idx].copy(), p.requests[idx].copy(), p.creation_ns[idx].copy(), [p.uids[i] for i in idx])
+    pods = Pods(p.class_id[idx].copy(), p.requests[idx].copy(), p.creation_ns[idx].copy(), [p.uids[i] for i in idx],
+                None if p.volumes is None else [list(p.volumes[i]) for i in idx])
     return Problem(prob.catalog, prob.nodepools, prob.classes, pods, prob.existing, prob.max_instance_types,
                    prob.min_values_policy, list(prob.bound))
 
