@@ -404,7 +404,12 @@ kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out);
  * once.  The fast-loop event counts keep their meaning: n_batches, n_noinv and n_winmove count what the general loop
  * would have counted for the same pods, whichever loop handled them (a step of j pods counts j batches and j
  * "no inversion" sorts), so batches - inner-loop pods + slow-path pods = entries to the general loop; [22] quick check
- * holds the checks and batches of both loops (n up to 49). */
+ * holds the checks and batches of both loops.
+ * [49] bound skips (always exact): slow-path candidates rejected by the headroom bound of their NodeClaim — on some
+ * axis the pod's request exceeds what the largest remaining option leaves — without an evaluation.  They are counted
+ * in kp_solve_stats.nodeclaim_evals like the evaluations they replace, and in neither [16] nor [19].
+ * Profiling only: [50] candidate rounds made of such candidates alone, [51] rounds that mix them with evaluated ones
+ * (n up to 52). */
 kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n);
 
 /*

@@ -7,6 +7,7 @@
 
 #include <type_traits>
 
+#include "kp_bound.h"
 #include "kp_device.h"
 #include "kp_eval.h"
 #include "kp_gosort.h"
@@ -159,6 +160,8 @@ struct FfdShared {
     int relaxed;                   // a pod relaxed since wave 0 last loaded its queue window (its lastLens are stale)
     uint64_t born;                 // late topology identities created so far (KpDev.tg_late)
     int xstart;                    // every existing node < xstart has rejected the current shape
+    int fwd;                       // the hand-off's collection passed rounds of virtual candidates (collect_candidates):
+                                   // the candidates it left are not the pod's first round (in the padding before cur_tol)
     uint64_t cur_tol;              // tolerations word of the current shape's class (bit 63: no requirement keys)
     int32_t cur_pq[KP_LDS_AXES];   // scaled quick-accept requests of the current shape
     int64_t shape_req[KP_MAX_R];   // requests of the current shape (pending-total flush)
@@ -445,63 +448,209 @@ __device__ inline void topo_record_quick(const KpDev& d, FfdShared& S, int c, in
 // skip it in the slice window.  Only wave 0 collects, and it writes the memo either inside its fast loop or while the
 // other waves are parked at the round's barrier, so no other wave reads the slice keys meanwhile (the PORTS variant
 // therefore takes the keys as a mutable pointer).
-template <bool TOPO, bool PORTS = false>
+// BOUND (ffd_solve: the 8-wave instantiations without reserved offerings, topology groups or PORTS), bound = the pod's
+// class has no topology terms: a collected candidate whose
+// NodeClaim the headroom bound rejects (kp_bound.h; DESIGN.md §4 "Headroom bound") is virtual — its entry of cand_pos
+// carries KP_CAND_VIRT, no wave evaluates it, and the round that would have evaluated it marks it in the shape's memo as
+// the evaluation would have.  A round of virtual candidates alone, with the scan not done, is not handed to the block:
+// every one of them would have been evaluated and rejected, so wave 0 marks them here, counts them and collects the
+// next round at once.  The pod's requests are S.pod_req, written by this wave before the call.
+#define KP_CAND_VIRT 0x40000000  // slice positions are below 65,536
+#ifndef KP_BOUND_SWEEP
+#define KP_BOUND_SWEEP 0      // A/B builds: 1 = bound_row_store sweeps the option words per axis (slower)
+#endif
+#ifndef KP_BOUND_IDLE_WAVE
+#define KP_BOUND_IDLE_WAVE 1  // A/B builds: 0 = the committing wave computes the in-flight commit's row itself
+#endif
+// One wave, after a collection left cnt (1 .. 8) candidates in S.cand_pos[buf]: the headroom bound on each of them.  Lane
+// 8 i + a takes axis a (r: its resource, the caller's act_axis(d, a)) of candidate i: the entry of its NodeClaim's bound
+// row and its request total (exact: flushed and waited for before every collection) are independent loads, one round
+// trip for the whole round.  A rejected candidate becomes virtual (KP_CAND_VIRT).  When
+// all are rejected and the scan is not done (sdone = 0), the parent evaluates and rejects every one of them (memo_ok: no
+// topology, no reserved offerings), so they are marked in the memo and counted here, and 1 is returned: the caller collects
+// the next round at once.  Out of line, like existing_volume_scan: its registers stay out of the plan of wave 0's fast
+// loop and of the evaluation rounds.
+template <bool PROF>
+static __device__ __attribute__((noinline)) int bound_round(const int64_t* __restrict__ nc_bound,
+                                                            const int64_t* __restrict__ nc_req,
+                                                            int R, int A,
+                                                            FfdShared& S, uint32_t* key, const uint16_t* ord, int buf,
+                                                            int cnt, int sdone, int r) {
+    static_assert(KP_NWAVES <= 8 && KP_LDS_AXES <= KP_BOUND_STRIDE && KP_BOUND_STRIDE == 8, "lane = 8 candidate + axis");
+    const int lane = (int)__lane_id(), ci = lane >> 3, ai = lane & 7;
+    const bool v = ci < cnt && ai < A;
+    const int nc = ord[S.cand_pos[buf][ci < cnt ? ci : 0]];
+    const int64_t b = v ? __hip_atomic_load(const_cast<int64_t*>(&nc_bound[(size_t)nc * KP_BOUND_STRIDE + ai]), __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT) : KP_NO_BOUND;
+    const int64_t tot = v ? ld_req(&nc_req[(size_t)nc * R + r]) : 0;
+    const uint64_t m = ballot(v && kp_bound_rejects(b, tot, S.pod_req[r]));
+    if (!m) return 0;
+    uint64_t vm = 0;
+    for (int i = 0; i < 8; i++)
+        if ((m >> (8 * i)) & 0xFFull) vm |= 1ull << i;
+    const int nv = __popcll(vm);
+    const int p = lane < cnt ? S.cand_pos[buf][lane] : 0;
+    const bool rej = (vm >> lane) & 1ull;
+    if (nv == cnt && !sdone) {
+        if (rej) key[p] |= 0x80000000u;
+        if (lane == 0) {
+            S.st[ST_NC_EVALS] += cnt;
+            S.st[ST_BOUND_SKIPS] += cnt;
+            if (PROF) S.st[ST_BOUND_ALLV]++;
+            S.fwd = 1;
+        }
+        return 1;
+    }
+    if (rej) S.cand_pos[buf][lane] = p | KP_CAND_VIRT;
+    if (PROF && lane == 0) S.st[nv == cnt ? ST_BOUND_ALLV : ST_BOUND_MIXED]++;
+    return 0;
+}
+template <bool TOPO, bool PORTS = false, bool BOUND = false, bool PROF = false>
 __device__ inline bool collect_candidates(const KpDev& d, FfdShared& S,
-                                          std::conditional_t<PORTS, uint32_t*, const uint32_t*> key, const uint16_t* ord,
-                                          const uint8_t* stmpl, uint64_t tol, int N, int start, int buf, int lane,
-                                          int pc = -1) {
-    int cnt = 0, pos = start, next = N;
+                                          std::conditional_t<PORTS || BOUND, uint32_t*, const uint32_t*> key,
+                                          const uint16_t* ord, const uint8_t* stmpl, uint64_t tol, int N, int start, int buf,
+                                          int lane, int pc = -1, bool bound = false) {
+    int pos = start;
     bool marked = false;
-    const int tp_n = TOPO ? S.tp_n : 0;  // read once: the stores to cand_pos below would make every use a new LDS read
-    // topology pods: at most d.topo_cands candidates per round (the first prefilter survivor usually accepts; fewer waves
-    // evaluating leaves each its own SIMD)
-    const int L = tp_n ? d.topo_cands : KP_NWAVES;
-    while (pos < N) {
-        const int p = pos + lane;
-        bool c = p < N && !(key[p] >> 31);
-        if (c) c = (tol >> stmpl[ord[p]]) & 1ull;
-        if (PORTS && pc >= 0) {
-            const bool meet = c && ports_meet(d, d.nc_ports + (size_t)ord[p] * d.PW, pc);
-            if constexpr (PORTS)
-                if (meet) key[p] |= 0x80000000u;
-            marked |= ballot(meet) != 0;
-            c = c && !meet;
-        }
-        if (tp_n && c) c = topo_prefilter_pass(d, S, ord[p]);
-        const uint64_t m0 = __ballot(c);
-        if (tp_n && m0 && cnt + __popcll(m0) < L) {
-            // topology pods: the first prefilter survivor usually accepts; end the round with this window rather than
-            // paying the prefilter's loads for up to 8 candidates (the next round continues after it)
-            const int rank = cnt + __popcll(m0 & ((1ull << lane) - 1ull));
-            if (c) S.cand_pos[buf][rank] = p;
-            cnt += __popcll(m0);
-            pos += 64;
-            if (lane == 0) {
-                S.n_cand[buf] = cnt;
-                S.scan_next[buf] = pos < N ? pos : N;
-                S.scan_done[buf] = pos >= N;
+    for (;;) {  // one round; BOUND: once more after a round of virtual candidates alone, from the position behind it
+        int cnt = 0, next = N;
+        const int tp_n = TOPO ? S.tp_n : 0;  // read once: the stores to cand_pos below would make every use a new LDS read
+        // topology pods: at most d.topo_cands candidates per round (the first prefilter survivor usually accepts; fewer waves
+        // evaluating leaves each its own SIMD)
+        const int L = tp_n ? d.topo_cands : KP_NWAVES;
+        while (pos < N) {
+            const int p = pos + lane;
+            bool c = p < N && !(key[p] >> 31);
+            if (c) c = (tol >> stmpl[ord[p]]) & 1ull;
+            if (PORTS && pc >= 0) {
+                const bool meet = c && ports_meet(d, d.nc_ports + (size_t)ord[p] * d.PW, pc);
+                if constexpr (PORTS)
+                    if (meet) key[p] |= 0x80000000u;
+                marked |= ballot(meet) != 0;
+                c = c && !meet;
             }
-            return marked;
+            if (tp_n && c) c = topo_prefilter_pass(d, S, ord[p]);
+            const uint64_t m0 = __ballot(c);
+            if (tp_n && m0 && cnt + __popcll(m0) < L) {
+                // topology pods: the first prefilter survivor usually accepts; end the round with this window rather than
+                // paying the prefilter's loads for up to 8 candidates (the next round continues after it)
+                const int rank = cnt + __popcll(m0 & ((1ull << lane) - 1ull));
+                if (c) S.cand_pos[buf][rank] = p;
+                cnt += __popcll(m0);
+                pos += 64;
+                if (lane == 0) {
+                    S.n_cand[buf] = cnt;
+                    S.scan_next[buf] = pos < N ? pos : N;
+                    S.scan_done[buf] = pos >= N;
+                }
+                return marked;
+            }
+            const uint64_t m = __ballot(c);
+            const int rank = cnt + __popcll(m & ((1ull << lane) - 1ull));
+            if (c && rank < L) S.cand_pos[buf][rank] = p;
+            const int tot = cnt + __popcll(m);
+            if (tot >= L) {
+                const uint64_t last = __ballot(c && rank == L - 1);
+                next = pos + __ffsll((unsigned long long)last);  // position after the last collected candidate
+                cnt = L;
+                break;
+            }
+            cnt = tot;
+            pos += 64;
         }
-        const uint64_t m = __ballot(c);
-        const int rank = cnt + __popcll(m & ((1ull << lane) - 1ull));
-        if (c && rank < L) S.cand_pos[buf][rank] = p;
-        const int tot = cnt + __popcll(m);
-        if (tot >= L) {
-            const uint64_t last = __ballot(c && rank == L - 1);
-            next = pos + __ffsll((unsigned long long)last);  // position after the last collected candidate
-            cnt = L;
-            break;
+        const bool sdone = (cnt < L) || next >= N;
+        if constexpr (BOUND) {
+            if (bound && cnt > 0 && d.lds_A > 0) {
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // cand_pos above
+                if (bound_round<PROF>(d.nc_bound, d.nc_req, d.R, d.lds_A, S, key, ord,
+                                            buf, cnt, sdone, act_axis(d, lane & 7))) {
+                    marked = true;
+                    pos = next;
+                    continue;
+                }
+            }
         }
-        cnt = tot;
-        pos += 64;
+        if (lane == 0) {
+            S.n_cand[buf] = cnt;
+            S.scan_next[buf] = cnt == L ? next : N;
+            S.scan_done[buf] = sdone;
+        }
+        return marked;
     }
-    if (lane == 0) {
-        S.n_cand[buf] = cnt;
-        S.scan_next[buf] = cnt == L ? next : N;
-        S.scan_done[buf] = (cnt < L) || next >= N;
+}
+
+// One wave: the headroom bound row of NodeClaim nc from the options and the witness an accepted Add left in ws
+// (kp_bound.h).  An axis' largest allocatable over the options is that of the first option in the axis' types ranked by
+// allocatable, largest first (d.alloc_rank): 64 ranks per step, lane k tests rank base + k against the option words, the
+// axes still searching side by side, so a step is one round trip whatever the number of axes.  Options only shrink, so
+// no axis finds an option before the step at which the NodeClaim's previous row found its first: entry
+// KP_BOUND_STRIDE - 1 of the row keeps that step and the walk resumes there (fresh: a NodeClaim being created walks
+// from the top, at most lds_tpad / 64 steps, when its NodePool's types rank low).  Read by collect_candidates behind the
+// barrier that ends the slow-path iteration.
+static __device__ __attribute__((noinline)) void bound_row_store(const KpDev* __restrict__ dp, const int64_t* alloc,
+                                                                 const WaveScratch& ws, int nc, int fresh) {
+    static_assert(KP_LDS_AXES < KP_BOUND_STRIDE, "the row's last entry holds the walk's first step");
+    const KpDev& d = *dp;
+    const int lane = (int)__lane_id();
+    const int A = d.lds_A, TP = d.lds_tpad;
+    const uint16_t* const rank = d.alloc_rank;
+    int64_t* const row = d.nc_bound + (size_t)nc * KP_BOUND_STRIDE;
+    int64_t mx[KP_LDS_AXES];
+#if KP_BOUND_SWEEP
+    // A/B builds: the per-axis max in lanes over the option words, then wave_max64 (commit_tmpl's subtractMax pattern)
+    const int start = 0, first = 0;
+    for (int ai = 0; ai < KP_LDS_AXES; ai++) {
+        mx[ai] = KP_NO_BOUND;
+        if (ai >= A) continue;
+        int64_t m = INT64_MIN;
+        for (int w = 0; w < d.TW; w++)
+            if ((ws.opts[w] >> lane) & 1ull) {
+                const int64_t av = alloc[ai * TP + w * 64 + lane];
+                m = av > m ? av : m;
+            }
+        mx[ai] = wave_max64(m);
     }
-    return marked;
+#else
+    int t[KP_LDS_AXES];
+    // the top step's ranks are loaded beside the resume step, not behind it: most NodeClaims resume at the top
+#pragma unroll
+    for (int ai = 0; ai < KP_LDS_AXES; ai++) {
+        mx[ai] = KP_NO_BOUND;
+        t[ai] = ai < A ? (int)rank[ai * TP + lane] : 0xFFFF;
+    }
+    const int start = fresh ? 0 : (int)__hip_atomic_load(&row[KP_BOUND_STRIDE - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int base = start * 64;
+    if (start > 0) {
+#pragma unroll
+        for (int ai = 0; ai < KP_LDS_AXES; ai++) t[ai] = ai < A ? (int)rank[ai * TP + base + lane] : 0xFFFF;
+    }
+    uint32_t pending = (1u << A) - 1u;
+    int first = -1;
+    while (base < TP) {
+#pragma unroll
+        for (int ai = 0; ai < KP_LDS_AXES; ai++)
+            if ((pending >> ai) & 1u) {
+                const uint64_t m = ballot(t[ai] < TP && ((ws.opts[t[ai] < TP ? t[ai] >> 6 : 0] >> (t[ai] & 63)) & 1ull));
+                if (m) {
+                    mx[ai] = alloc[ai * TP + rl32(t[ai], __ffsll((unsigned long long)m) - 1)];
+                    pending &= ~(1u << ai);
+                    if (first < 0) first = base >> 6;
+                }
+            }
+        base += 64;
+        if (!pending || base >= TP) break;
+#pragma unroll
+        for (int ai = 0; ai < KP_LDS_AXES; ai++) t[ai] = ((pending >> ai) & 1u) ? (int)rank[ai * TP + base + lane] : 0xFFFF;
+    }
+#endif
+    int64_t mine = KP_NO_BOUND;  // (an axis with no option at all, which an accepted Add cannot have, gives no bound)
+#pragma unroll
+    for (int ai = 0; ai < KP_LDS_AXES; ai++)
+        if (lane == ai) mine = mx[ai];
+    if (lane < A)
+        __hip_atomic_store(&row[lane], kp_bound_entry(mine, ws.hr[lane] >= 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == KP_BOUND_STRIDE - 1)
+        __hip_atomic_store(&row[lane], (int64_t)(first < 0 ? start : first), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // types whose Capacity exceeds a NodePool's remaining limits (filterByRemainingResources)
@@ -741,6 +890,11 @@ __device__ inline void block_sort_move(FfdShared& S, SortSlice sl, int tid, int 
 template <bool RESV, bool TOPO, bool PREF, bool HBM = false, bool PROF = false, bool PORTS = false>
 __device__ __forceinline__ void ffd_solve(KpDev d) {
     constexpr bool TOPO_ON = KP_TOPO_ON && TOPO;  // the solve has topology groups
+    // the headroom bound on slow-path candidates (collect_candidates): compiled out of the PORTS instantiations, whose
+    // 8-wave kernels have no register to spare (as LEAN below), of the topology instantiations, and of the RESV ones,
+    // where NodeClaims with live reservations are exempt and the test costs more than it skips; the
+    // node-dense preference kernel (PREF && HBM) spills VGPRs with it
+    constexpr bool BOUND = !PORTS && !TOPO && !RESV && !(PREF && HBM);
     const bool prof = PROF && d.profile;
     int* const trace = PROF ? d.trace : nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -864,6 +1018,9 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
         for (int i = 0; i < KP_MAX_R; i++) S.shape_req[i] = 0;
         for (int i = 0; i < ST_COUNT; i++) S.st[i] = 0;
     }
+    // eval_wave returns from its toleration test before it sets memo_ok: a wave whose first candidate fails there reads
+    // what the LDS held.  These kernels never clear it (no topology narrowing), so it is 1 from the start.
+    if (BOUND && lane == 0) S.ws[wave].memo_ok = 1;
     __syncthreads();
     EvalEnv E;
     E.pt = nullptr;
@@ -1598,7 +1755,13 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     S.cls_fill = S.CC.cls != c;  // decided before the barrier: fill_class_cache rewrites CC.cls
                     S.topo_pod = 0;
                 }
-                if (collect_candidates<TOPO_ON, PORTS>(d, S, skey, sord, stmpl, ~0ull, N, f, 0, lane, (PORTS && cport) ? c : -1))
+                // the bound test reads the candidates' request totals: the flushed ones have reached L2 (the wait the
+                // write-back below would make)
+                if (BOUND) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (BOUND && lane == 0) S.fwd = 0;
+                // (a pod with topology terms left the loop above: the bound applies to every pod that gets here)
+                if (collect_candidates<TOPO_ON, PORTS, BOUND, PROF>(d, S, skey, sord, stmpl, ~0ull, N, f, 0, lane,
+                                                                          (PORTS && cport) ? c : -1, BOUND))
                     any_rej = 1;
                 break;
             }
@@ -1883,7 +2046,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
         int first = 0;  // round-0 candidates already evaluated
         bool team_won = false;
         if ((KP_TEAM_FIRST_RESV | !RESV) && (KP_TEAM_FIRST_TOPO | !TOPO))
-        if (!team && d.team_first && S.n_cand[0] > 0) {
+        // (a virtual candidate 0 is rejected without it: the parallel round marks and counts it with the others.  After
+        // rounds of virtual candidates alone — S.fwd — that was the pod's first candidate, and the round at hand is a
+        // later one: its candidates are all evaluated, and marked, in parallel)
+        if (!team && d.team_first && S.n_cand[0] > 0 && !(BOUND && ((S.cand_pos[0][0] & KP_CAND_VIRT) || S.fwd))) {
             const int nc = sord[S.cand_pos[0][0]];
             const int tm = d.nc_tmpl[nc];
             const bool fast0 = !(S.CC.flags & CF_TOPO) && !(RESV && d.resv_on && ld_i32(&d.nc_rlive[nc])) &&
@@ -1930,7 +2096,16 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             const int b = round & 1;
             const int f0 = round == 0 ? first : 0;  // candidate index of wave 0
             const int ci = wave + f0;
-            if (ci < S.n_cand[b]) {
+            if (BOUND && ci < S.n_cand[b] && (S.cand_pos[b][ci] & KP_CAND_VIRT)) {
+                // a virtual candidate (collect_candidates): rejected for good without an evaluation
+                if (lane == 0) {
+                    S.fastp[b][ci] = 0;
+                    S.acc[b][ci] = 0;
+                    skey[S.cand_pos[b][ci] & ~KP_CAND_VIRT] |= 0x80000000u;
+                    S.any_rej = 1;
+                    atomicAdd((unsigned long long*)&S.st[ST_BOUND_SKIPS], 1ull);
+                }
+            } else if (ci < S.n_cand[b]) {
                 const int nc = sord[S.cand_pos[b][ci]];
                 EvalIn a;
                 a.Ahdr = d.nc_hdr + (size_t)nc * K;
@@ -1986,8 +2161,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             if (tid == 0) S.st[ST_NC_EVALS] += nc_ > f0 ? nc_ - f0 : 0;
             if (win >= 0 || S.scan_done[b]) break;
             if (wave == 0 &&
-                collect_candidates<TOPO_ON, PORTS>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N, S.scan_next[b],
-                                                   b ^ 1, lane, (PORTS && (S.CC.flags & CF_PORTS)) ? S.cur_cls : -1) && lane == 0)
+                collect_candidates<TOPO_ON, PORTS, BOUND, PROF>(d, S, skey, sord, stmpl, S.topo_pod ? d.tol[S.cur_cls] : ~0ull, S.N,
+                                                                      S.scan_next[b], b ^ 1, lane,
+                                                                      (PORTS && (S.CC.flags & CF_PORTS)) ? S.cur_cls : -1,
+                                                                      BOUND && !(S.CC.flags & CF_TOPO)) && lane == 0)
                 S.any_rej = 1;
             __syncthreads();
             round++;
@@ -2004,6 +2181,14 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
         if (win >= 0) {
             // the wave whose scratch holds the accepted Add (team: every wave's does)
             const int cw = (team || team_won) ? 0 : win - (round == 0 ? first : 0);
+            // the winner's bound row, by an idle wave beside the commit: the accepted Add's options and witness are in the
+            // winner's scratch behind the round's barrier (a team's in every wave's own, with no barrier behind its last
+            // join), and the commit only reads them
+            if (BOUND && wave == (cw + KP_BOUND_IDLE_WAVE) % KP_NWAVES)
+            {
+                bound_row_store(d.self, E.alloc, S.ws[(team || team_won) ? wave : cw], sord[S.cand_pos[round & 1][win]], 0);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row has landed before the iteration's barrier
+            }
             if (wave == cw) {
                 const int pos = S.cand_pos[round & 1][win];
                 const int nc = sord[pos];
@@ -2075,6 +2260,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     __hip_atomic_store(&d.nc_req[(size_t)n * R + r], d.daemon[(size_t)jj * R + r] + S.pod_req[r],
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (lane < A && n < NQ) shr[lane * NQ + n] = S.ws[cw].hr[lane];
+                if (BOUND) bound_row_store(d.self, E.alloc, S.ws[cw], n, 1);
                 // subtractMax(remaining, nodeClaim.InstanceTypeOptions)
                 for (int r = 0; r < R; r++) {
                     if (!d.limit_set[(size_t)jj * R + r]) continue;
@@ -2228,6 +2414,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                             __hip_atomic_store(&d.nc_req[(size_t)n * R + r], d.daemon[(size_t)jj * R + r] + S.pod_req[r],
                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (lane < A && n < NQ) shr[lane * NQ + n] = S.ws[wave].hr[lane];
+                        if (BOUND) bound_row_store(d.self, E.alloc, S.ws[wave], n, 1);
                         // subtractMax(remaining, nodeClaim.InstanceTypeOptions)
                         for (int r = 0; r < R; r++) {
                             if (!d.limit_set[(size_t)jj * R + r]) continue;

@@ -32,6 +32,7 @@
 #include "kp_launch.h"
 #include "kp_layout.h"
 
+#include "kp_bound.h"
 #include "kp_host.h"  // the kernel launchers' prototypes
 
 namespace {
@@ -433,7 +434,7 @@ struct kp_ctx {
     double ns_prep = 0, ns_exec = 0, ns_fin = 0;
     hipEvent_t ev[6] = {};
     double kernel_ms[5] = {};
-    int64_t cycles[44] = {};  // FFD phases (s_memtime): pop, sort, scan+eval, templates, commit, full pdqsort
+    int64_t cycles[47] = {};  // FFD phases (s_memtime): pop, sort, scan+eval, templates, commit, full pdqsort
     bool any_min_values = false;             // some template requirement carries minValues
     int max_min_values = 0;                  // the largest minValues among the template requirements
     bool min_multi = false;                  // ... on a multi-valued catalog key (zone, capacity type, ...)
@@ -520,6 +521,8 @@ struct kp_ctx {
     DBuf<uint32_t> d_type_ro;
     DBuf<uint64_t> d_nc_held;
     DBuf<int32_t> d_rcap0, d_nc_rlive;
+    DBuf<uint16_t> d_alloc_rank;  // [axes][TP] types by allocatable, largest first (KpDev::alloc_rank)
+    DBuf<int64_t> d_nc_bound;  // [NCcap][KP_BOUND_STRIDE] headroom bound rows of the in-flight NodeClaims (kp_bound.h)
     DBuf<double> d_ro_price;
     DBuf<int32_t> d_trace;                   // KPSIM_TRACE_POD diagnostics
     std::string launch_err;
@@ -3004,6 +3007,7 @@ static kp_status solve_plan_nodeclaims(kp_ctx* ctx, const kp_solve_input* in, So
     HIPCHK(c->d_nc_tmpl.ensure(NCcap));
     HIPCHK(c->d_nc_held.ensure((size_t)NCcap * std::max(1, c->h_ro.ridw)));
     HIPCHK(c->d_nc_rlive.ensure(NCcap));
+    HIPCHK(c->d_nc_bound.ensure((size_t)NCcap * KP_BOUND_STRIDE));
     if (se.PW > 0) HIPCHK(c->d_nc_ports.ensure((size_t)NCcap * se.PW));
     HIPCHK(c->d_qbuf.ensure(std::max(P, 1)));
     HIPCHK(c->d_last_len.ensure(std::max(P, 1)));
@@ -3455,6 +3459,20 @@ static kp_status solve_fill_dev(kp_ctx* ctx, const kp_solve_input* in, SolveEnc&
         }
         d.qshift[ai] = sh;
     }
+    {  // the staged axes' types ranked by allocatable, largest first (bound_row_store): [axes][TP], TP = 64-padded T
+        const int TP = (T + 63) / 64 * 64, ns = std::min(d.n_active, KP_LDS_AXES);
+        static_assert(KP_MAX_TYPES < 0xFFFF, "alloc_rank holds type ids as u16, 0xFFFF is its padding");
+        std::vector<uint16_t> rank((size_t)std::max(ns, 1) * TP, 0xFFFF);
+        std::vector<int> ord(T);
+        for (int ai = 0; ai < ns; ai++) {
+            const int64_t* al = &c->alloc_rt[(size_t)d.active_axes[ai] * T];
+            for (int t = 0; t < T; t++) ord[t] = t;
+            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return al[x] > al[y]; });
+            for (int t = 0; t < T; t++) rank[(size_t)ai * TP + t] = (uint16_t)ord[t];
+        }
+        HIPCHK(c->d_alloc_rank.upload(rank, s));
+        d.alloc_rank = c->d_alloc_rank.p;
+    }
     d.ro = c->h_ro.n > 0 ? c->d_ro.p : nullptr;
     DEV(type_ro); DEV(ro_price);
     d.ro_n = c->h_ro.n;
@@ -3462,7 +3480,7 @@ static kp_status solve_fill_dev(kp_ctx* ctx, const kp_solve_input* in, SolveEnc&
     d.ro_nrid = c->h_ro.nrid;
     d.ro_ridw = c->h_ro.ridw;
     d.resv_on = (c->reserved_capacity && c->h_ro.n > 0) ? 1 : 0;
-    DEV(rcap0); DEV(nc_held); DEV(nc_rlive);
+    DEV(rcap0); DEV(nc_held); DEV(nc_rlive); DEV(nc_bound);
     d.alloc_act = nullptr;
     if (NCcap > KP_NC_FIRST || T > 1024) {  // node-dense plan or large catalog: the staged axes' allocatable table in HBM
                                             // ([axes][TP], TP = 64-padded T) when LDS cannot hold it
@@ -3743,6 +3761,9 @@ extern "C" kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out) {
     c->cycles[41] = st[ST_N_INNER];
     c->cycles[42] = st[ST_CYC_QINNER];
     c->cycles[43] = st[ST_N_MULTI];
+    c->cycles[44] = st[ST_BOUND_SKIPS];
+    c->cycles[45] = st[ST_BOUND_ALLV];
+    c->cycles[46] = st[ST_BOUND_MIXED];
     if (getenv("KPSIM_PROFILE") && st[ST_SLOW_WHY] + st[ST_SLOW_WHY + 1] + st[ST_SLOW_WHY + 2] + st[ST_SLOW_WHY + 3])
         fprintf(stderr, "[kpsim] slow-path pods: no candidate %lld, class not absorbed %lld, witness short %lld, no witness table %lld; "
                 "no-op merge quick accepts %lld; placed by the first candidate %lld, a later one %lld, the templates %lld; "
@@ -3794,7 +3815,7 @@ extern "C" kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n) {
     if (!ctx || !ms) return KP_E_INVALID;
     if (!ctx->executed) return fail(ctx, KP_E_STATE, "no execute yet");
     for (int i = 0; i < n && i < 5; i++) ms[i] = ctx->kernel_ms[i];
-    for (int i = 5; i < n && i < 49; i++) ms[i] = (double)ctx->cycles[i - 5];
+    for (int i = 5; i < n && i < 52; i++) ms[i] = (double)ctx->cycles[i - 5];
     return KP_OK;
 }
 

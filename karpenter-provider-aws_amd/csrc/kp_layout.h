@@ -328,6 +328,9 @@ struct KpDev {
     const int32_t* rcap0;            // [ro_nrid] ReservationManager capacity per reservation (least over its offerings)
     uint64_t* nc_held;               // [NCcap][ro_ridw] reservations a NodeClaim holds (NodeClaim.reservedOfferings' IDs)
     int32_t* nc_rlive;               // [NCcap] the NodeClaim's options keep a compatible available reserved offering
+    const uint16_t* alloc_rank;      // [lds_A][lds_tpad] per staged axis the types by allocatable, largest first (0xFFFF: padding)
+    int64_t* nc_bound;               // [NCcap][KP_BOUND_STRIDE] headroom bound rows (kp_bound.h): per staged axis the largest
+                                     // allocatable over the NodeClaim's options, written by the slow path's commits
 
     // a device copy of this struct (uploaded before each FFD launch): out-of-line device functions take it instead of
     // the kernel argument, whose address would otherwise escape and put every field read of the kernel in scratch
@@ -366,11 +369,17 @@ struct KpDev {
 // stats slots
 enum {
     ST_POPPED = 0, ST_NC_EVALS, ST_NC_SCANNED, ST_TMPL_EVALS, ST_EXIST_EVALS, ST_SORT_FAST, ST_SORT_FULL,
-    ST_MEMO_SKIPS, ST_CYC_POP, ST_CYC_SORT, ST_CYC_SCAN, ST_CYC_TMPL, ST_CYC_COMMIT, ST_CYC_SORT_FULL,
+    ST_BOUND_MIXED, ST_CYC_POP, ST_CYC_SORT, ST_CYC_SCAN, ST_CYC_TMPL, ST_CYC_COMMIT, ST_CYC_SORT_FULL,
     // KPSIM_PROFILE: pods that wave 0's same-shape inner loop took without a pass through the general loop, and the cycles
     // of their steps from the end of one batch to the next check (pending move, scan from f, pop); ST_N_MULTI: the steps
     // of that loop that placed several pods on the element at f at once
     ST_N_INNER = 14, ST_CYC_QINNER, ST_N_MULTI = 22,
+    // bound skips (always exact): slow-path candidates the headroom bound rejected without an evaluation (kp_bound.h);
+    // KPSIM_PROFILE: the candidate rounds whose candidates were all such (ST_BOUND_ALLV: every one but a scan's last
+    // costs no block round) and those that held some beside real candidates (ST_BOUND_MIXED)
+    // (23, 31 and ST_BOUND_MIXED = 7, the former unused ST_MEMO_SKIPS, were free slots: FfdShared and the LDS plan keep
+    // their size, as with ST_HANDOFF_WB; the host hands them out side by side, kp_last_kernel_times [49..51])
+    ST_BOUND_SKIPS = 23, ST_BOUND_ALLV = 31,
     ST_EV_REQ = 16, ST_EV_MASK, ST_EV_OFF, ST_EV_TYPES, ST_EV_MIN, ST_EV_CALLS,
     ST_QUICK = 24, ST_SLOW, ST_WITNESS_MISS, ST_CYC_QPOP, ST_CYC_QSCAN, ST_CYC_QCHECK, ST_CYC_QCOMMIT,
     ST_N_NOINV = 32, ST_N_WINMOVE, ST_N_LDSSORT, ST_N_PIVOT, ST_N_WINLOAD, ST_N_FLUSH, ST_N_SHAPE, ST_EXIST_PLACED = 44,

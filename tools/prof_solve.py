@@ -21,7 +21,10 @@ NAMES = ["cyc_fast_loop", "cyc_sort", "cyc_slow_eval", "cyc_templates", "-", "cy
          "cyc_ho_entry", "cyc_ho_failed_check", "cyc_ho_flush_collect", "cyc_ho_writeback",
          # wave 0's same-shape inner loop (kp_layout.h ST_N_INNER): pods it took without a pass through the general loop
          # and the cycles of their steps; cyc_q_check holds the checks and batches of both loops
-         "n_inner", "cyc_q_inner", "n_multi"]
+         "n_inner", "cyc_q_inner", "n_multi",
+         # slow-path candidates the headroom bound rejected without an evaluation (kp_layout.h ST_BOUND_SKIPS, always
+         # exact), the candidate rounds made of them alone and the rounds that mix them with evaluated candidates
+         "bound_skips", "rounds_all_virtual", "rounds_mixed"]
 
 
 def ffd_counters(ctx):
