@@ -783,6 +783,72 @@ kp_status kp_catalog_free(kp_catalog* cat);
  */
 kp_status kp_result_nodeclaim_requirements(kp_ctx* ctx, int32_t nc, char* buf, int64_t cap, int64_t* needed);
 
+/*
+ * Explanations — what scheduling.Results.PodErrors says about a pod the Solve left unschedulable.  [core] Solve stops
+ * after a full queue cycle without a placement, so such a pod made its last add() against the state the Solve ended
+ * in, and its error is the list of that add()'s per-NodeClaimTemplate failures (existing nodes and in-flight
+ * NodeClaims contribute nothing to it).  kp_solve_explain recomputes those failures on the device from that final
+ * state, read-only: one row per (reported pod, NodePool), grouped by pod in ascending pod index, a pod's rows in
+ * template order (weight descending, name ascending).  Each row holds the FIRST stage that fails, in core's order:
+ * the limit filter of scheduler.add, then inside NodeClaim.Add taints, host ports, Compatible, topology, the
+ * instance-type filter (over all options, without short-circuit, as filterResults keeps it), minValues on what
+ * remains, and the reservation step.  `fits` is pod requests + the template's daemon overhead against allocatable.
+ * The pod is evaluated in its final relaxation stage.  Under MIN_VALUES_POLICY=BestEffort KP_WHY_MIN_VALUES never
+ * appears.  INTEGRATION.md maps (reason, criteria) to core's wording.
+ *
+ * KP_WHY_RESERVED is the residual of a live reservation step: every other stage passes at the final state and a
+ * remaining type has a compatible available reserved offering (ReservationManager capacities are not kept after the
+ * Solve).  Any other residual is KP_WHY_UNKNOWN (a reason is never guessed).
+ *
+ * Two limits of what the final state can say:
+ *   - a pod that kp_solve_fetch reports unschedulable because FinalizeScheduling dropped its NodeClaim (minValues not
+ *     met after truncation) was placed by its last add(); its rows are KP_WHY_UNKNOWN with every other field 0 / -1 and
+ *     nothing is evaluated for it (the state that NodeClaim shaped would give a wrong reason);
+ *   - topology identities that only relaxed pods create are taken as created when a pod ended in or passed through a
+ *     stage that owns them; where such an identity has variants (owners differing in node filter or minDomains), which
+ *     variant exists is rebuilt in pod order, not in the order the Solve created them, so TOPOLOGY rows of classes under
+ *     such variants are approximate.
+ */
+enum { KP_WHY_UNKNOWN = 0,      /* the final state decides nothing (see above) */
+       KP_WHY_LIMITS,           /* filterByRemainingResources left no option: "all available instance types exceed limits" */
+       KP_WHY_TAINTS,           /* the pod does not tolerate the template's taints */
+       KP_WHY_HOST_PORTS,       /* a port of the pod conflicts with the template's daemonset ports */
+       KP_WHY_REQUIREMENTS,     /* Compatible(template requirements, pod requirements) fails; `key` names the key */
+       KP_WHY_TOPOLOGY,         /* Topology.AddRequirements, or the Compatible check after it, fails */
+       KP_WHY_INSTANCE_TYPES,   /* filterInstanceTypesByRequirements left nothing; `criteria` says how */
+       KP_WHY_MIN_VALUES,       /* types remain but miss minValues under the Strict policy; `key` names the key */
+       KP_WHY_RESERVED };       /* offeringsToReserve in strict mode: a compatible reserved offering, none reservable */
+
+typedef struct kp_pod_explanation {
+    int32_t pod, nodepool;      /* index into the input's pods / nodepools */
+    int32_t reason;             /* KP_WHY_* */
+    int32_t key;                /* REQUIREMENTS / MIN_VALUES: a key of kp_solve_explain_key (when several keys fail, the
+                                   one whose name sorts first; a kubernetes.io/hostname In / DoesNotExist / Gt / Lt
+                                   never meets a new NodeClaim's placeholder and is one of them); else -1 */
+    uint32_t criteria;          /* INSTANCE_TYPES: bit0 requirementsMet, bit1 fits, bit2 hasOffering,
+                                   bit3 requirementsAndFits, bit4 requirementsAndOffering, bit5 fitsAndOffering; else 0 */
+    int32_t n_options;          /* options the new NodeClaim starts from (template options within remaining limits);
+                                   0 with a reason past LIMITS: the NodePool's own requirements leave no instance type
+                                   (core skips such a NodePool at NewScheduler) */
+    int32_t n_requirements, n_fits, n_offering;   /* of those, how many meet each criterion on its own (0 when an
+                                                     earlier stage failed) */
+} kp_pod_explanation;
+
+/* Valid from kp_solve_execute until the ctx's next prepare, catalog upload or availability patch (KP_E_STATE outside).
+ * pods == NULL: every unschedulable pod (n_pods is ignored); else the listed pods as a set (KP_E_INVALID for an index
+ * out of range or a pod that was scheduled).  *needed receives the row count; KP_E_BUFFER when cap is smaller (nothing
+ * is launched).  A Solve with nothing unschedulable: KP_OK, *needed == 0.  The call changes nothing: a kp_solve_fetch
+ * after it returns what it returned before, a second call returns the same rows. */
+kp_status kp_solve_explain(kp_ctx* ctx, int32_t n_pods, const int32_t* pods, kp_pod_explanation* out, int64_t cap,
+                           int64_t* needed);
+/* Name of key `key` of the explained solve's key table (valid as long as kp_solve_explain is), NUL-terminated;
+ * *needed receives the size incl. NUL, KP_E_BUFFER when cap is smaller, KP_E_INVALID for an index outside the table. */
+kp_status kp_solve_explain_key(kp_ctx* ctx, int32_t key, char* buf, int64_t cap, int64_t* needed);
+/* The last kp_solve_explain: ms[0] device time of its kernel (HIP events), ms[1] the whole call;
+ * counters[0] (shape, NodePool) pairs the kernel evaluated = distinct final shapes among the reported pods x NodePools,
+ * [1] those shapes, [2] pods reported.  n_counters up to 3. */
+kp_status kp_solve_explain_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters);
+
 #ifdef __cplusplus
 }
 #endif

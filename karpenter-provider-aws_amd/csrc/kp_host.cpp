@@ -605,6 +605,19 @@ struct kp_ctx {
     // last results (host)
     int last_N = 0, M = 0;
     std::vector<int32_t> h_nc_tmpl;
+    // kp_solve_explain: valid from an execute until a prepare, catalog upload or availability patch; its staging
+    // buffers, events (created on first use) and the last call's figures (kp_solve_explain_stats)
+    bool explain_ok = false;
+    std::vector<uint64_t> h_x_tol;           // [C] bit j: the class tolerates template j's taints (KpDev.tol before the
+    std::vector<uint8_t> h_x_hblock;         //     hostname fold); [C] the class's hostname requirement (not a class key)
+    int x_host_key = -1;                     //     is one no new NodeClaim's placeholder satisfies; the hostname key
+    DBuf<uint64_t> d_x_tol;
+    DBuf<uint8_t> d_x_hblock;
+    DBuf<int32_t> d_x_rep;
+    DBuf<KpExplainRow> d_x_rows;
+    hipEvent_t xev[2] = {};
+    double explain_ms[2] = {};
+    int64_t explain_counts[3] = {};
 };
 
 static kp_status fail(kp_ctx* c, kp_status st, const std::string& msg) {
@@ -711,6 +724,8 @@ extern "C" kp_status kp_ctx_destroy(kp_ctx* ctx) {
     for (auto& e : ctx->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->lev)
+        if (e) hipEventDestroy(e);
+    for (auto& e : ctx->xev)
         if (e) hipEventDestroy(e);
     if (ctx->lstream2) {
         hipStreamSynchronize(ctx->lstream2);
@@ -1199,6 +1214,7 @@ static kp_status patch_avail_one(kp_ctx* ctx, const uint8_t* available, int32_t 
     if (!ctx->have_catalog) return fail(ctx, KP_E_STATE, "no catalog");
     if (n != (int)ctx->off_type.size()) return fail(ctx, KP_E_INVALID, "offering count mismatch");
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->explain_ok = false;  // an explanation reads the availability the Solve ran with
     rebuild_avail(ctx, std::vector<uint8_t>(available, available + n));
     HIPCHK(ctx->d_avail_zc.upload(ctx->avail_zc, ctx->stream));
     std::fill(ctx->ro_avail.begin(), ctx->ro_avail.end(), 0ull);
@@ -2372,6 +2388,11 @@ static kp_status solve_template_tables(kp_ctx* ctx, const kp_solve_input* in, So
             }
         }
     }
+    // kp_solve_explain tells the two apart: the tolerations alone, and the classes whose hostname requirement refuses
+    // every NodeClaim (below they are folded into one mask for the Solve kernels)
+    ctx->h_x_tol = se.tol;
+    ctx->h_x_hblock = se.hblock;
+    ctx->x_host_key = se.hostname_key;
     for (int i = 0; i < C; i++)
         if (se.hblock[i]) se.tol[i] = 0;  // hostname requirement no new or in-flight NodeClaim can satisfy
     return KP_OK;
@@ -3551,6 +3572,7 @@ extern "C" kp_status kp_solve_prepare(kp_ctx* ctx, const kp_solve_input* in) try
     HIPCHK(hipSetDevice(ctx->device));
     kp_ctx* c = ctx;
     c->prepared = c->executed = false;
+    c->explain_ok = false;
     c->cons_prepared = false;
     SolveEnc se;
     STAGE(solve_expand);
@@ -3694,6 +3716,7 @@ extern "C" kp_status kp_solve_execute(kp_ctx* ctx) {
     }
     c->ns_exec = ns_since(t0);
     c->executed = true;
+    c->explain_ok = true;
     return KP_OK;
 }
 
@@ -3884,6 +3907,183 @@ static std::string reqs_text(const kp_ctx* ctx, const ReqHdr* h, const uint64_t*
     std::string s;
     for (auto& l : lines) s += l + "\n";
     return s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// solve: explanations (kp_explain.hip): why each NodePool refused the pods the Solve left unschedulable
+// ---------------------------------------------------------------------------------------------
+static_assert(KP_WHY_UNKNOWN == KPX_UNKNOWN && KP_WHY_LIMITS == KPX_LIMITS && KP_WHY_TAINTS == KPX_TAINTS &&
+                  KP_WHY_HOST_PORTS == KPX_HOST_PORTS && KP_WHY_REQUIREMENTS == KPX_REQUIREMENTS &&
+                  KP_WHY_TOPOLOGY == KPX_TOPOLOGY && KP_WHY_INSTANCE_TYPES == KPX_INSTANCE_TYPES &&
+                  KP_WHY_MIN_VALUES == KPX_MIN_VALUES && KP_WHY_RESERVED == KPX_RESERVED,
+              "kpsim.h KP_WHY_* and kp_explain.h KPX_* name the same reasons");
+
+// The late topology identities the executed Solve created: those of its start, then the ones of every stage a pod
+// relaxed into (Topology.Update).  The order of births matters to variant siblings alone; it is taken in pod order.
+static uint64_t explain_born(const kp_ctx* c, const std::vector<int32_t>& final_cls) {
+    uint64_t born = c->dev.born0;
+    if (c->tg_G <= 0 || c->tg_nlate <= 0 || c->pref.relax_next.empty()) return born;
+    const int C = (int)c->pref.relax_next.size();
+    for (int p = 0; p < c->P; p++)
+        for (int cl = c->p_pcls.p[p], hops = 0; cl >= 0 && cl < C && cl != final_cls[p] && hops < C; hops++) {
+            cl = c->pref.relax_next[cl];
+            if (cl >= 0 && cl < (int)c->h_cls_birth.size()) born = late_birth(c->h_late_sib, born, c->h_cls_birth[cl]);
+        }
+    return born;
+}
+
+extern "C" kp_status kp_solve_explain(kp_ctx* ctx, int32_t n_pods, const int32_t* pods, kp_pod_explanation* out,
+                                      int64_t cap, int64_t* needed) try {
+    if (!ctx || !needed || (pods && n_pods < 0)) return KP_E_INVALID;
+    if (!ctx->executed || !ctx->explain_ok)
+        return fail(ctx, KP_E_STATE, "kp_solve_explain needs the state of a kp_solve_execute (none since the last prepare, "
+                                     "catalog upload or availability patch)");
+    HIPCHK(hipSetDevice(ctx->device));
+    kp_ctx* c = ctx;
+    hipStream_t s = c->stream;
+    const auto t0 = clk::now();
+    const int P = c->P, NT = c->NT;
+    int32_t N = 0, err = 0;
+    HIPCHK(hipMemcpyAsync(&N, c->d_nc_count.p, sizeof N, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&err, c->d_err.p, sizeof err, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (err) return fail(ctx, KP_E_STATE, "the Solve did not complete (kp_solve_fetch reports why)");
+    std::vector<int32_t> pres(P), pshape(P), pcls(P), valid(std::max(N, 0));
+    if (P > 0) {
+        HIPCHK(hipMemcpyAsync(pres.data(), c->d_pod_result.p, P * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(pshape.data(), c->d_pod_shape.p, P * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(pcls.data(), c->d_pod_cls.p, P * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (N > 0) HIPCHK(hipMemcpyAsync(valid.data(), c->d_nc_valid.p, N * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    // as kp_solve_fetch reports it: no placement, or one on a NodeClaim FinalizeScheduling dropped
+    auto unsched = [&](int p) { return pres[p] == KP_POD_UNSCHEDULABLE || (pres[p] >= 0 && (pres[p] >= N || !valid[pres[p]])); };
+    std::vector<int32_t> list;
+    if (!pods) {
+        for (int p = 0; p < P; p++)
+            if (unsched(p)) list.push_back(p);
+    } else {
+        for (int i = 0; i < n_pods; i++) {
+            const int p = pods[i];
+            if (p < 0 || p >= P) return fail(ctx, KP_E_INVALID, "kp_solve_explain: pod index " + std::to_string(p) + " out of range");
+            if (!unsched(p)) return fail(ctx, KP_E_INVALID, "kp_solve_explain: pod " + std::to_string(p) + " was scheduled");
+            list.push_back(p);
+        }
+        std::sort(list.begin(), list.end());
+        list.erase(std::unique(list.begin(), list.end()), list.end());
+    }
+    c->explain_ms[0] = c->explain_ms[1] = 0;
+    c->explain_counts[0] = c->explain_counts[1] = c->explain_counts[2] = 0;
+    *needed = (int64_t)list.size() * NT;
+    if (*needed == 0) return KP_OK;
+    if (!out || cap < *needed) return fail(ctx, KP_E_BUFFER, "kp_solve_explain: " + std::to_string(*needed) + " rows");
+    // a row is a function of (final shape, template): one representative pod per distinct shape
+    // (a pod whose NodeClaim FinalizeScheduling dropped was placed by its last add(): the final state, which that
+    // NodeClaim shaped, says nothing about it; it is not evaluated and its rows stay KP_WHY_UNKNOWN: of_pod -1)
+    std::vector<int32_t> rep, of_pod(list.size());
+    {
+        std::unordered_map<int32_t, int32_t> idx;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (pres[list[i]] >= 0) {
+                of_pod[i] = -1;
+                continue;
+            }
+            const auto it = idx.emplace(pshape[list[i]], (int32_t)rep.size());
+            if (it.second) rep.push_back(list[i]);
+            of_pod[i] = it.first->second;
+        }
+    }
+    const int S = (int)rep.size();
+    HIPCHK(c->d_x_rep.upload(rep, s));
+    HIPCHK(c->d_x_rows.ensure((size_t)S * NT));
+    if ((int)c->h_x_tol.size() < c->C || (int)c->h_x_hblock.size() < c->C)
+        return fail(ctx, KP_E_STATE, "kp_solve_explain: the prepared solve kept no toleration table");
+    HIPCHK(c->d_x_tol.upload(c->h_x_tol, s));
+    HIPCHK(c->d_x_hblock.upload(c->h_x_hblock, s));
+    for (auto& e : c->xev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    KpExplain x{};
+    x.rep = c->d_x_rep.p;
+    x.n_shapes = S;
+    x.born = explain_born(c, pcls);
+    x.tol = c->d_x_tol.p;
+    x.hblock = c->d_x_hblock.p;
+    x.rows = c->d_x_rows.p;
+    HIPCHK(hipEventRecord(c->xev[0], s));
+    HIPCHK(kp_launch_explain(c->dev, x, s));
+    HIPCHK(hipEventRecord(c->xev[1], s));
+    std::vector<KpExplainRow> rows((size_t)S * NT);
+    HIPCHK(hipMemcpyAsync(rows.data(), c->d_x_rows.p, rows.size() * sizeof(KpExplainRow), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float kms = 0;
+    HIPCHK(hipEventElapsedTime(&kms, c->xev[0], c->xev[1]));
+    // the failing key with the smallest name (kmask: class keys of the shape's class / entries of the template's min_keys)
+    std::vector<int32_t> koff, ckeys, mkeys;
+    auto key_of = [&](const KpExplainRow& r, int cls, int j) -> int {
+        int best = -1;
+        for (uint32_t m = r.kmask; m; m &= m - 1) {
+            const int i = __builtin_ctz(m);
+            const int k = r.reason == KPX_MIN_VALUES ? mkeys[(size_t)j * KP_MAX_CLASS_KEYS + i] : ckeys[koff[cls] + i];
+            if (k >= 0 && (best < 0 || c->sol.keys[k].name < c->sol.keys[best].name)) best = k;
+        }
+        // the hostname requirement is no class key (the Solve folds it into the toleration mask): it fails too
+        const int hk = c->x_host_key;
+        if (r.reason == KPX_REQUIREMENTS && r.hostkey && hk >= 0 && (best < 0 || c->sol.keys[hk].name < c->sol.keys[best].name))
+            best = hk;
+        return best;
+    };
+    bool need_keys = false;
+    for (const KpExplainRow& r : rows) need_keys |= r.kmask != 0;  // (a hostname-only failure needs no table)
+    if (need_keys) {
+        koff.resize(c->C + NT + 1);
+        HIPCHK(hipMemcpy(koff.data(), c->d_cls_koff.p, koff.size() * 4, hipMemcpyDeviceToHost));
+        ckeys.resize(std::max(koff.back(), 1));
+        if (koff.back() > 0) HIPCHK(hipMemcpy(ckeys.data(), c->d_cls_keys.p, (size_t)koff.back() * 4, hipMemcpyDeviceToHost));
+        mkeys.resize((size_t)NT * KP_MAX_CLASS_KEYS);
+        HIPCHK(hipMemcpy(mkeys.data(), c->d_min_keys.p, mkeys.size() * 4, hipMemcpyDeviceToHost));
+    }
+    for (size_t i = 0; i < list.size(); i++)
+        for (int j = 0; j < NT; j++) {
+            static const KpExplainRow none{};  // KPX_UNKNOWN
+            const KpExplainRow& r = of_pod[i] >= 0 ? rows[(size_t)of_pod[i] * NT + j] : none;
+            kp_pod_explanation& o = out[i * NT + j];
+            o.pod = list[i];
+            o.nodepool = c->tmpl_np[j];
+            o.reason = r.reason;
+            o.key = (r.kmask || r.hostkey) ? key_of(r, pcls[rep[of_pod[i]]], j) : -1;
+            o.criteria = r.criteria;
+            o.n_options = r.n_options;
+            o.n_requirements = r.n_requirements;
+            o.n_fits = r.n_fits;
+            o.n_offering = r.n_offering;
+        }
+    c->explain_ms[0] = kms;
+    c->explain_ms[1] = ns_since(t0) * 1e-6;
+    c->explain_counts[0] = (int64_t)S * NT;
+    c->explain_counts[1] = S;
+    c->explain_counts[2] = (int64_t)list.size();
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_solve_explain_key(kp_ctx* ctx, int32_t key, char* buf, int64_t cap, int64_t* needed) {
+    if (!ctx) return KP_E_INVALID;
+    if (!ctx->executed || !ctx->explain_ok) return fail(ctx, KP_E_STATE, "kp_solve_explain_key without an explainable solve");
+    if (key < 0 || key >= ctx->K || key >= (int)ctx->sol.keys.size()) return fail(ctx, KP_E_INVALID, "key index");
+    const std::string& s = ctx->sol.keys[key].name;
+    if (needed) *needed = (int64_t)s.size() + 1;
+    if ((int64_t)s.size() + 1 > cap || !buf) return KP_E_BUFFER;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return KP_OK;
+}
+
+extern "C" kp_status kp_solve_explain_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters) {
+    if (!ctx || !ms) return KP_E_INVALID;
+    ms[0] = ctx->explain_ms[0];
+    ms[1] = ctx->explain_ms[1];
+    for (int i = 0; counters && i < n_counters && i < 3; i++) counters[i] = ctx->explain_counts[i];
+    return KP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kp_cons.h"
+#include "kp_explain.h"
 #include "kp_launch.h"
 #include "kp_layout.h"
 
@@ -14,6 +15,7 @@ hipError_t kp_launch_class_mask(const KpDev& d, hipStream_t s);
 hipError_t kp_launch_template_init(const KpDev& d, hipStream_t s);
 hipError_t kp_launch_existing(const KpDev& d, hipStream_t s);
 hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s);
+hipError_t kp_launch_explain(const KpDev& d, const KpExplain& x, hipStream_t s);
 hipError_t kp_ffd_set_attributes();
 hipError_t kp_cons_set_attributes();
 hipError_t kp_launch_finalize(const KpDev& d, int n_nodeclaims, hipStream_t s);

@@ -196,6 +196,28 @@ PROBE_DTYPE = np.dtype([("decision", np.int32), ("valid", np.int32), ("all_sched
 assert PROBE_DTYPE.itemsize == C.sizeof(kp_probe_result)
 
 
+# kp_solve_explain: why a NodePool refused an unschedulable pod (kpsim.h KP_WHY_*, kp_pod_explanation)
+(KP_WHY_UNKNOWN, KP_WHY_LIMITS, KP_WHY_TAINTS, KP_WHY_HOST_PORTS, KP_WHY_REQUIREMENTS, KP_WHY_TOPOLOGY,
+ KP_WHY_INSTANCE_TYPES, KP_WHY_MIN_VALUES, KP_WHY_RESERVED) = range(9)
+WHY_NAMES = ["UNKNOWN", "LIMITS", "TAINTS", "HOST_PORTS", "REQUIREMENTS", "TOPOLOGY", "INSTANCE_TYPES", "MIN_VALUES",
+             "RESERVED"]
+# kp_pod_explanation.criteria (filterResults)
+(KP_CRIT_REQUIREMENTS, KP_CRIT_FITS, KP_CRIT_OFFERING, KP_CRIT_REQUIREMENTS_AND_FITS, KP_CRIT_REQUIREMENTS_AND_OFFERING,
+ KP_CRIT_FITS_AND_OFFERING) = (1, 2, 4, 8, 16, 32)
+
+
+class kp_pod_explanation(C.Structure):
+    _fields_ = [("pod", C.c_int32), ("nodepool", C.c_int32), ("reason", C.c_int32), ("key", C.c_int32),
+                ("criteria", C.c_uint32), ("n_options", C.c_int32), ("n_requirements", C.c_int32),
+                ("n_fits", C.c_int32), ("n_offering", C.c_int32)]
+
+
+EXPLANATION_DTYPE = np.dtype([("pod", np.int32), ("nodepool", np.int32), ("reason", np.int32), ("key", np.int32),
+                              ("criteria", np.uint32), ("n_options", np.int32), ("n_requirements", np.int32),
+                              ("n_fits", np.int32), ("n_offering", np.int32)])
+assert EXPLANATION_DTYPE.itemsize == C.sizeof(kp_pod_explanation)
+
+
 KP_FILTER_NAMES = ["compatible-available-filter", "capacity-reservation-type-filter", "capacity-block-filter",
                    "reserved-offering-filter", "exotic-instance-filter", "spot-instance-filter"]  # filter.go Name()
 KP_N_FILTERS = 6

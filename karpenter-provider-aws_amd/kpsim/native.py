@@ -14,6 +14,7 @@ EXPORTS = [
     "kp_consolidate_stats", "kp_consolidate_prepare", "kp_consolidate_execute", "kp_launch_select", "kp_launch_stats",
     "kp_nodeclaim_labels", "kp_catalog_build", "kp_catalog_get_view", "kp_catalog_overhead", "kp_catalog_resource_name",
     "kp_catalog_free", "kp_consolidate_command", "kp_consolidate_replacement", "kp_solve_volume_encoding",
+    "kp_solve_explain", "kp_solve_explain_key", "kp_solve_explain_stats",
 ]
 
 _lib = None
@@ -48,6 +49,11 @@ def load():
     if hasattr(L, "kp_solve_volume_encoding"):  # (absent from older libraries, A/B only)
         L.kp_solve_volume_encoding.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     L.kp_solve_execute.argtypes = [C.c_void_p]
+    if hasattr(L, "kp_solve_explain"):  # (absent from older libraries, A/B only)
+        L.kp_solve_explain.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.kp_pod_explanation),
+                                       C.c_int64, C.POINTER(C.c_int64)]
+        L.kp_solve_explain_key.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.kp_solve_explain_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
     L.kp_solve_fetch.argtypes = [C.c_void_p, C.POINTER(abi.kp_solve_output)]
     L.kp_result_nodeclaim_requirements.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
     L.kp_last_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
@@ -180,6 +186,44 @@ class Context:
             out[name] = a.view(np.uint64) if name.endswith("mask") else a
             pos += n if VD > 0 else 0
         return out
+
+    def explain(self, pods=None):
+        """kp_solve_explain of the executed Solve: one row per (unschedulable pod, NodePool) as a numpy array of
+        abi.EXPLANATION_DTYPE, grouped by pod in ascending pod index, a pod's rows in template order.  pods=None: every
+        unschedulable pod; else the listed ones (KP_E_INVALID for a scheduled pod or an index out of range)."""
+        import numpy as np
+        need = C.c_int64(0)
+        n, lst = 0, None
+        if pods is not None:
+            self._x_pods = np.ascontiguousarray(pods, np.int32)
+            n, lst = len(self._x_pods), self._x_pods.ctypes.data_as(C.POINTER(C.c_int32))
+        st = self.L.kp_solve_explain(self.h, n, lst, None, 0, C.byref(need))
+        if st not in (abi.KP_OK, abi.KP_E_BUFFER):
+            self.check(st, "kp_solve_explain")
+        out = np.zeros(max(1, need.value), abi.EXPLANATION_DTYPE)
+        if need.value:
+            self.check(self.L.kp_solve_explain(self.h, n, lst, out.ctypes.data_as(C.POINTER(abi.kp_pod_explanation)),
+                                               len(out), C.byref(need)), "kp_solve_explain")
+        return out[:need.value]
+
+    def explain_key(self, key):
+        """Name of key `key` of kp_pod_explanation.key (kp_solve_explain_key)."""
+        need = C.c_int64(0)
+        buf = C.create_string_buffer(256)
+        st = self.L.kp_solve_explain_key(self.h, key, buf, len(buf), C.byref(need))
+        if st == abi.KP_E_BUFFER:
+            buf = C.create_string_buffer(need.value)
+            st = self.L.kp_solve_explain_key(self.h, key, buf, len(buf), C.byref(need))
+        self.check(st, "kp_solve_explain_key")
+        return buf.value.decode()
+
+    def explain_stats(self):
+        """(ms[kernel, whole call], counters[(shape, NodePool) pairs evaluated, distinct shapes, pods reported]) of the
+        last explain()."""
+        ms = (C.c_double * 2)()
+        ct = (C.c_int64 * 3)()
+        self.check(self.L.kp_solve_explain_stats(self.h, ms, ct, 3), "kp_solve_explain_stats")
+        return list(ms), list(ct)
 
     def fetch(self, out_buffers):
         self.check(self.L.kp_solve_fetch(self.h, C.byref(out_buffers.view)), "kp_solve_fetch")

@@ -32,6 +32,23 @@ class SolveResults:
     raw: model.Results
 
 
+@dataclass
+class Explanation:
+    """One per-NodePool failure of an unschedulable pod's last add() (kpsim.h kp_pod_explanation)."""
+    nodepool: str
+    reason: int                     # abi.KP_WHY_*
+    key: Optional[str]              # REQUIREMENTS / MIN_VALUES: the label key
+    criteria: int                   # INSTANCE_TYPES: abi.KP_CRIT_* bits
+    n_options: int
+    n_requirements: int
+    n_fits: int
+    n_offering: int
+
+    @property
+    def reason_name(self):
+        return abi.WHY_NAMES[self.reason]
+
+
 class Scheduler:
     def __init__(self, catalog: List[model.InstanceType], device=0, ctx: Optional[native.Context] = None):
         self.ctx = ctx or native.Context(device)
@@ -40,6 +57,7 @@ class Scheduler:
         self.ctx.upload_catalog(self.catalog_view)
 
     def solve_raw(self, prob: model.Problem) -> model.Results:
+        self._nodepools = [np_.name for np_ in prob.nodepools]  # explain() names them
         iv = model.SolveInputView(prob)
         cap_nc = max(16, min(prob.pods.n + 1, 8192))
         m = prob.max_instance_types if prob.max_instance_types > 0 else len(self.catalog)
@@ -55,6 +73,22 @@ class Scheduler:
             out = model.OutputBuffers(prob.pods.n, max(1, v.n_nodeclaims), max(1, v.n_type_ids))
             self.ctx.fetch(out)
         return out.results()
+
+    def explain(self, pods=None) -> Dict[int, List[Explanation]]:
+        """Why each NodePool refused the pods the last Solve left unschedulable: pod -> one Explanation per NodePool in
+        template order (what core lists under Results.PodErrors[pod]).  pods=None: every such pod.  Solve() does not
+        call it; it is valid until the next Solve on this Scheduler's context."""
+        rows = self.ctx.explain(pods)
+        names: Dict[int, str] = {}
+        out: Dict[int, List[Explanation]] = {}
+        for r in rows:
+            k = int(r["key"])
+            if k >= 0 and k not in names:
+                names[k] = self.ctx.explain_key(k)
+            out.setdefault(int(r["pod"]), []).append(Explanation(
+                self._nodepools[int(r["nodepool"])], int(r["reason"]), names.get(k), int(r["criteria"]),
+                int(r["n_options"]), int(r["n_requirements"]), int(r["n_fits"]), int(r["n_offering"])))
+        return out
 
     def Solve(self, prob: model.Problem) -> SolveResults:
         r = self.solve_raw(prob)
