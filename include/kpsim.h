@@ -409,7 +409,9 @@ kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out);
  * axis the pod's request exceeds what the largest remaining option leaves — without an evaluation.  They are counted
  * in kp_solve_stats.nodeclaim_evals like the evaluations they replace, and in neither [16] nor [19].
  * Profiling only: [50] candidate rounds made of such candidates alone, [51] rounds that mix them with evaluated ones
- * (n up to 52). */
+ * (n up to 52).  In the kernels that carry the bound (they have no topology section) [36] is not a cycle count: it
+ * counts the in-flight commits that stored their NodeClaim's bound row again because an axis' largest type left the
+ * options; the other in-flight commits left the row alone. */
 kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n);
 
 /*

@@ -462,6 +462,12 @@ __device__ inline void topo_record_quick(const KpDev& d, FfdShared& S, int c, in
 #ifndef KP_BOUND_IDLE_WAVE
 #define KP_BOUND_IDLE_WAVE 1  // A/B builds: 0 = the committing wave computes the in-flight commit's row itself
 #endif
+#ifndef KP_BOUND_ROW_SKIP
+#define KP_BOUND_ROW_SKIP 1   // A/B builds: 0 = every in-flight commit walks the rank table and stores its row
+#endif
+#ifndef KP_BOUND_TMPL_IDLE
+#define KP_BOUND_TMPL_IDLE 1  // A/B builds: 0 = the committing wave computes a new NodeClaim's row itself, walking from rank 0
+#endif
 // One wave, after a collection left cnt (1 .. 8) candidates in S.cand_pos[buf]: the headroom bound on each of them.  Lane
 // 8 i + a takes axis a (r: its resource, the caller's act_axis(d, a)) of candidate i: the entry of its NodeClaim's bound
 // row and its request total (exact: flushed and waited for before every collection) are independent loads, one round
@@ -579,26 +585,49 @@ __device__ inline bool collect_candidates(const KpDev& d, FfdShared& S,
     }
 }
 
-// One wave: the headroom bound row of NodeClaim nc from the options and the witness an accepted Add left in ws
-// (kp_bound.h).  An axis' largest allocatable over the options is that of the first option in the axis' types ranked by
-// allocatable, largest first (d.alloc_rank): 64 ranks per step, lane k tests rank base + k against the option words, the
-// axes still searching side by side, so a step is one round trip whatever the number of axes.  Options only shrink, so
-// no axis finds an option before the step at which the NodeClaim's previous row found its first: entry
-// KP_BOUND_STRIDE - 1 of the row keeps that step and the walk resumes there (fresh: a NodeClaim being created walks
-// from the top, at most lds_tpad / 64 steps, when its NodePool's types rank low).  Read by collect_candidates behind the
-// barrier that ends the slow-path iteration.
+// One wave: the headroom bound row of a NodeClaim (row: its line of d.nc_bound) from the options and the witness an
+// accepted Add left in ws (kp_bound.h).  An axis' largest allocatable over the options is that of the first option in the
+// axis' types ranked by allocatable, largest first (rank: d.alloc_rank): 64 ranks per step, lane k tests rank base + k
+// against the option words, the axes still searching side by side, so a step is one round trip whatever the number of
+// axes.  Options only shrink, so no axis finds an option before the step at which the NodeClaim's previous row found its
+// first: the row's tail keeps that step and the walk resumes there (fresh: a NodeClaim being created walks from the top,
+// at most lds_tpad / 64 steps, when its NodePool's types rank low).  The tail also keeps the type found per axis
+// (KP_BOUND_ROW_SKIP): while the accepted options hold every one of them, and the witness flags are the stored ones, the
+// walk would find the same types at the same steps, so the row is left as it is: one load of the line, no rank step, no
+// store and nothing for the caller's vmcnt(0) to wait for.  A fresh row is always computed and stored whole, so a row a
+// previous solve left at the NodeClaim's index is never compared against.  Read by collect_candidates behind the barrier
+// that ends the slow-path iteration.
+// fresh_step < 0: an in-flight commit.  fresh_step >= 0: a NodeClaim being created; its walk starts at that step
+// (d.tmpl_bstep of its template: no type the template can offer ranks before it on any axis; 0: from the top).
+// Out of line (as bound_round): its registers stay out of the plan of the commit.  PROF (the diagnostic twin):
+// st[ST_BOUND_ROWS] counts the in-flight commits that store their row; the production instantiation ignores st.
+template <bool PROF>
 static __device__ __attribute__((noinline)) void bound_row_store(const KpDev* __restrict__ dp, const int64_t* alloc,
-                                                                 const WaveScratch& ws, int nc, int fresh) {
-    static_assert(KP_LDS_AXES < KP_BOUND_STRIDE, "the row's last entry holds the walk's first step");
+                                                                 const WaveScratch& ws, int nc, int fresh_step, long long* st) {
+    static_assert(KP_LDS_AXES <= KP_BOUND_STRIDE - 2 && KP_LDS_AXES <= KP_BOUND_TAIL_AXES, "the row's last two entries hold its tail");
     const KpDev& d = *dp;
     const int lane = (int)__lane_id();
     const int A = d.lds_A, TP = d.lds_tpad;
     const uint16_t* const rank = d.alloc_rank;
     int64_t* const row = d.nc_bound + (size_t)nc * KP_BOUND_STRIDE;
     int64_t mx[KP_LDS_AXES];
+    int start = fresh_step < 0 ? 0 : fresh_step;
+    if (fresh_step < 0) {
+        const int64_t e = lane < KP_BOUND_STRIDE ? __hip_atomic_load(&row[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        const uint64_t lo = rl64((uint64_t)e, KP_BOUND_STRIDE - 2), hi = rl64((uint64_t)e, KP_BOUND_STRIDE - 1);
+#if KP_BOUND_ROW_SKIP
+        const bool kept = lane >= A || kp_bound_axis_kept(kp_bound_tail_type(lo, hi, lane), ws.opts, TP >> 6, e, ws.hr[lane] >= 0);
+        if (!ballot(!kept)) return;
+        if (PROF && lane == 0) atomicAdd((unsigned long long*)&st[ST_BOUND_ROWS], 1ull);
+#endif
+        start = (int)kp_bound_tail_step(hi);
+    }
+    KpBoundTail tail = kp_bound_tail_empty(0);
 #if KP_BOUND_SWEEP
-    // A/B builds: the per-axis max in lanes over the option words, then wave_max64 (commit_tmpl's subtractMax pattern)
-    const int start = 0, first = 0;
+    // A/B builds: the per-axis max in lanes over the option words, then wave_max64 (commit_tmpl's subtractMax pattern);
+    // the tail names no type, so every commit computes the row
+    const int first = 0;
+    start = 0;
     for (int ai = 0; ai < KP_LDS_AXES; ai++) {
         mx[ai] = KP_NO_BOUND;
         if (ai >= A) continue;
@@ -612,17 +641,11 @@ static __device__ __attribute__((noinline)) void bound_row_store(const KpDev* __
     }
 #else
     int t[KP_LDS_AXES];
-    // the top step's ranks are loaded beside the resume step, not behind it: most NodeClaims resume at the top
+    int base = start * 64;
 #pragma unroll
     for (int ai = 0; ai < KP_LDS_AXES; ai++) {
         mx[ai] = KP_NO_BOUND;
-        t[ai] = ai < A ? (int)rank[ai * TP + lane] : 0xFFFF;
-    }
-    const int start = fresh ? 0 : (int)__hip_atomic_load(&row[KP_BOUND_STRIDE - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int base = start * 64;
-    if (start > 0) {
-#pragma unroll
-        for (int ai = 0; ai < KP_LDS_AXES; ai++) t[ai] = ai < A ? (int)rank[ai * TP + base + lane] : 0xFFFF;
+        t[ai] = (ai < A && base < TP) ? (int)rank[ai * TP + base + lane] : 0xFFFF;
     }
     uint32_t pending = (1u << A) - 1u;
     int first = -1;
@@ -632,7 +655,9 @@ static __device__ __attribute__((noinline)) void bound_row_store(const KpDev* __
             if ((pending >> ai) & 1u) {
                 const uint64_t m = ballot(t[ai] < TP && ((ws.opts[t[ai] < TP ? t[ai] >> 6 : 0] >> (t[ai] & 63)) & 1ull));
                 if (m) {
-                    mx[ai] = alloc[ai * TP + rl32(t[ai], __ffsll((unsigned long long)m) - 1)];
+                    const int ty = rl32(t[ai], __ffsll((unsigned long long)m) - 1);
+                    mx[ai] = alloc[ai * TP + ty];
+                    kp_bound_tail_set(tail, ai, (unsigned)ty);
                     pending &= ~(1u << ai);
                     if (first < 0) first = base >> 6;
                 }
@@ -643,14 +668,16 @@ static __device__ __attribute__((noinline)) void bound_row_store(const KpDev* __
         for (int ai = 0; ai < KP_LDS_AXES; ai++) t[ai] = ((pending >> ai) & 1u) ? (int)rank[ai * TP + base + lane] : 0xFFFF;
     }
 #endif
+    tail.hi = (tail.hi & 0x0000FFFFFFFFFFFFull) | ((uint64_t)(unsigned)(first < 0 ? start : first) << 48);
     int64_t mine = KP_NO_BOUND;  // (an axis with no option at all, which an accepted Add cannot have, gives no bound)
 #pragma unroll
     for (int ai = 0; ai < KP_LDS_AXES; ai++)
         if (lane == ai) mine = mx[ai];
     if (lane < A)
         __hip_atomic_store(&row[lane], kp_bound_entry(mine, ws.hr[lane] >= 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (lane == KP_BOUND_STRIDE - 1)
-        __hip_atomic_store(&row[lane], (int64_t)(first < 0 ? start : first), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == KP_BOUND_STRIDE - 2 || lane == KP_BOUND_STRIDE - 1)
+        __hip_atomic_store(&row[lane], (int64_t)(lane == KP_BOUND_STRIDE - 2 ? tail.lo : tail.hi), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // types whose Capacity exceeds a NodePool's remaining limits (filterByRemainingResources)
@@ -2186,7 +2213,8 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             // join), and the commit only reads them
             if (BOUND && wave == (cw + KP_BOUND_IDLE_WAVE) % KP_NWAVES)
             {
-                bound_row_store(d.self, E.alloc, S.ws[(team || team_won) ? wave : cw], sord[S.cand_pos[round & 1][win]], 0);
+                bound_row_store<PROF>(d.self, E.alloc, S.ws[(team || team_won) ? wave : cw], sord[S.cand_pos[round & 1][win]], -1,
+                                      S.st);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row has landed before the iteration's barrier
             }
             if (wave == cw) {
@@ -2260,7 +2288,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     __hip_atomic_store(&d.nc_req[(size_t)n * R + r], d.daemon[(size_t)jj * R + r] + S.pod_req[r],
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (lane < A && n < NQ) shr[lane * NQ + n] = S.ws[cw].hr[lane];
-                if (BOUND) bound_row_store(d.self, E.alloc, S.ws[cw], n, 1);
+                if (BOUND && !KP_BOUND_TMPL_IDLE) bound_row_store<PROF>(d.self, E.alloc, S.ws[cw], n, 0, S.st);
                 // subtractMax(remaining, nodeClaim.InstanceTypeOptions)
                 for (int r = 0; r < R; r++) {
                     if (!d.limit_set[(size_t)jj * R + r]) continue;
@@ -2296,6 +2324,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 // the templates one at a time in weight order, each evaluated by the whole block (the type sweep split
                 // over the waves, as for a team candidate): the first that accepts wins, and every wave's scratch holds
                 // its Add
+                // the index of the NodeClaim a template opens, read while no wave can be past the winning evaluation's
+                // join: wave 0 raises S.N at the end of its commit, beside which other waves still run the lines below
+                // (the kernels without the bound keep reading S.N where they did)
+                const int n_new = BOUND ? S.N : 0;
                 for (int j = 0; j < d.NT; j++) {
                     uint64_t o = (lane < TW && d.tmpl_ok[j]) ? d.tmpl_opts[(size_t)j * TW + lane] : 0;
                     o = limit_filter(d, j, o, lane);
@@ -2335,9 +2367,15 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                         break;
                     }
                 }
-                if (twin >= 0 && (S.N >= NCMAX || S.N >= d.NCcap)) {
+                if (twin >= 0 && ((BOUND ? n_new : S.N) >= NCMAX || (BOUND ? n_new : S.N) >= d.NCcap)) {
                     if (tid == 0) S.err = 1;
                     twin = -1;
+                }
+                // the new NodeClaim's bound row, by an idle wave beside the commit (every wave's scratch holds the team's
+                // Add): it walks from the template's step, not from rank 0, and has landed before the iteration's barrier
+                if (BOUND && KP_BOUND_TMPL_IDLE && twin >= 0 && wave == KP_BOUND_IDLE_WAVE % KP_NWAVES) {
+                    bound_row_store<PROF>(d.self, E.alloc, S.ws[wave], n_new, d.tmpl_bstep[twin], S.st);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
                 if (twin >= 0 && wave == 0) commit_tmpl(twin, 0);
             } else
@@ -2414,7 +2452,9 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                             __hip_atomic_store(&d.nc_req[(size_t)n * R + r], d.daemon[(size_t)jj * R + r] + S.pod_req[r],
                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (lane < A && n < NQ) shr[lane * NQ + n] = S.ws[wave].hr[lane];
-                        if (BOUND) bound_row_store(d.self, E.alloc, S.ws[wave], n, 1);
+                        // (one template per wave: the winner's scratch alone holds the Add, so it stores the row itself)
+                        if (BOUND)
+                            bound_row_store<PROF>(d.self, E.alloc, S.ws[wave], n, KP_BOUND_TMPL_IDLE ? d.tmpl_bstep[jj] : 0, S.st);
                         // subtractMax(remaining, nodeClaim.InstanceTypeOptions)
                         for (int r = 0; r < R; r++) {
                             if (!d.limit_set[(size_t)jj * R + r]) continue;

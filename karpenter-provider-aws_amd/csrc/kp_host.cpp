@@ -521,6 +521,7 @@ struct kp_ctx {
     DBuf<uint32_t> d_type_ro;
     DBuf<uint64_t> d_nc_held;
     DBuf<int32_t> d_rcap0, d_nc_rlive;
+    DBuf<int32_t> d_tmpl_bstep;  // [NT] first rank step of each template's instance types (KpDev::tmpl_bstep)
     DBuf<uint16_t> d_alloc_rank;  // [axes][TP] types by allocatable, largest first (KpDev::alloc_rank)
     DBuf<int64_t> d_nc_bound;  // [NCcap][KP_BOUND_STRIDE] headroom bound rows of the in-flight NodeClaims (kp_bound.h)
     DBuf<double> d_ro_price;
@@ -3493,6 +3494,17 @@ static kp_status solve_fill_dev(kp_ctx* ctx, const kp_solve_input* in, SolveEnc&
         }
         HIPCHK(c->d_alloc_rank.upload(rank, s));
         d.alloc_rank = c->d_alloc_rank.p;
+        // per template the step at which the walk of a NodeClaim created from it starts: the first at which any of the
+        // template's instance types (se.rows: a superset of every option set it can hand out) appears on any staged axis
+        std::vector<int32_t> bstep(std::max(se.NT, 1), 0);
+        for (int j = 0; j < se.NT && ns > 0; j++) {
+            int st = TP / 64;
+            for (int ai = 0; ai < ns; ai++)
+                st = std::min(st, kp_bound_first_step(&rank[(size_t)ai * TP], TP, &se.rows[(size_t)j * ctx->TW]));
+            bstep[j] = st < TP / 64 ? st : 0;
+        }
+        HIPCHK(c->d_tmpl_bstep.upload(bstep, s));
+        d.tmpl_bstep = c->d_tmpl_bstep.p;
     }
     d.ro = c->h_ro.n > 0 ? c->d_ro.p : nullptr;
     DEV(type_ro); DEV(ro_price);

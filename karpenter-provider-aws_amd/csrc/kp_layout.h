@@ -329,6 +329,8 @@ struct KpDev {
     uint64_t* nc_held;               // [NCcap][ro_ridw] reservations a NodeClaim holds (NodeClaim.reservedOfferings' IDs)
     int32_t* nc_rlive;               // [NCcap] the NodeClaim's options keep a compatible available reserved offering
     const uint16_t* alloc_rank;      // [lds_A][lds_tpad] per staged axis the types by allocatable, largest first (0xFFFF: padding)
+    const int32_t* tmpl_bstep;       // [NT] per template the first rank step at which one of its instance types appears on any
+                                     // staged axis (kp_bound_first_step): where the walk of a NodeClaim created from it starts
     int64_t* nc_bound;               // [NCcap][KP_BOUND_STRIDE] headroom bound rows (kp_bound.h): per staged axis the largest
                                      // allocatable over the NodeClaim's options, written by the slow path's commits
 
@@ -380,6 +382,10 @@ enum {
     // (23, 31 and ST_BOUND_MIXED = 7, the former unused ST_MEMO_SKIPS, were free slots: FfdShared and the LDS plan keep
     // their size, as with ST_HANDOFF_WB; the host hands them out side by side, kp_last_kernel_times [49..51])
     ST_BOUND_SKIPS = 23, ST_BOUND_ALLV = 31,
+    // KPSIM_PROFILE: the in-flight commits that stored their NodeClaim's bound row again (some axis' largest type left the
+    // options, kp_bound.h); the others left it alone.  It shares the slot of ST_CYC_TSETUP: the kernels that carry the
+    // bound have no topology section, and the topology kernels carry no bound (kp_last_kernel_times [36])
+    ST_BOUND_ROWS = 46,
     ST_EV_REQ = 16, ST_EV_MASK, ST_EV_OFF, ST_EV_TYPES, ST_EV_MIN, ST_EV_CALLS,
     ST_QUICK = 24, ST_SLOW, ST_WITNESS_MISS, ST_CYC_QPOP, ST_CYC_QSCAN, ST_CYC_QCHECK, ST_CYC_QCOMMIT,
     ST_N_NOINV = 32, ST_N_WINMOVE, ST_N_LDSSORT, ST_N_PIVOT, ST_N_WINLOAD, ST_N_FLUSH, ST_N_SHAPE, ST_EXIST_PLACED = 44,
@@ -399,6 +405,7 @@ enum {
     // wait for the flushed request totals (ST_HANDOFF_WB: a free slot, so FfdShared and the LDS plan keep their size)
     ST_HANDOFF = 77, ST_HANDOFF_WB = 43, ST_COUNT = 80
 };
+static_assert(ST_BOUND_ROWS == ST_CYC_TSETUP, "ST_BOUND_ROWS shares the topology setup slot");
 // The stage cycles (ST_CYC_*, ST_EV_REQ .. ST_EV_MIN, ST_SEG, ST_TQ_CYC, ST_HANDOFF), the ST_N_* counters and the
 // ST_TQ_WHY / ST_SLOW_WHY breakdowns are written by the diagnostic twins of the Solve kernels alone (ffd_solve PROF) and
 // read 0 otherwise; every other slot is exact in both.

@@ -55,6 +55,10 @@ def main():
     ffd = dict(zip(NAMES, ffd_counters(ctx)))
     # entries to wave 0's general loop: one per batch that the inner loop did not start, one per pod handed to the block
     ffd["general_loop_entries"] = ffd["n_batches"] - ffd["n_inner"] + ffd["slow_pods"]
+    # the kernels that carry the headroom bound have no topology section and count, in the slot of its setup cycles, the
+    # in-flight commits that stored their NodeClaim's bound row again (kp_layout.h ST_BOUND_ROWS, kpsim.h [36])
+    if which == "config2":
+        ffd["bound_rows_stored"] = ffd.pop("cyc_topo_setup")
     print(json.dumps({"config": which, "pods": n, "wall_ms": wall, "kernel_ms": kt, "nodeclaims": r.n_nodeclaims, "stats": r.stats,
                       "ffd": ffd}, indent=1))
     ctx.close()
