@@ -851,6 +851,81 @@ kp_status kp_solve_explain_key(kp_ctx* ctx, int32_t key, char* buf, int64_t cap,
  * [1] those shapes, [2] pods reported.  n_counters up to 3. */
 kp_status kp_solve_explain_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters);
 
+/*
+ * Consolidation explanations — why a probe of a prepared pass found no command: what [core] disruption publishes as
+ * Unconsolidatable events (consolidation.go computeConsolidation / computeSpotToSpotConsolidation, recalled).  A
+ * kp_probe_result row says "not all pods scheduled" or "a second NodeClaim" at best; a kp_probe_explanation row holds the
+ * test of computeConsolidation's tail that ended the probe.  The tests run in core's order: not all non-pending pods
+ * scheduled, no new NodeClaim (DELETE), more than one NodeClaim, then either the spot-to-spot branch (gate, price filter,
+ * minValues, no cheaper option, fewer than 15 cheaper options for one candidate) or the price filter, minValues and "no
+ * cheaper option"; minValues is tested before "no cheaper option" in both branches.  Multi-node probes then run
+ * filterOutSameInstanceType.  A NodeClaim that TruncateInstanceTypes dropped (F_TRUNCATED) makes the probe
+ * PODS_UNSCHEDULABLE when it held a non-pending pod, else the decision is DELETE and the reason NONE.
+ *
+ * Known departure, the one n_new_nodeclaims already has: the device stops a probe at its second new NodeClaim, so
+ * KP_UNCONS_MULTIPLE_NODECLAIMS wins even where core would first have found an unschedulable pod later in the queue, and
+ * the NodeClaim count behind it is "2 or more".
+ */
+enum { KP_UNCONS_NONE = 0,                 /* the probe has a command: DELETE, or a valid REPLACE */
+       KP_UNCONS_PODS_UNSCHEDULABLE = 1,   /* !Results.AllNonPendingPodsScheduled() */
+       KP_UNCONS_MULTIPLE_NODECLAIMS = 2,  /* a second new NodeClaim (the device stops there, as today) */
+       KP_UNCONS_SPOT_TO_SPOT_DISABLED = 3,
+       KP_UNCONS_MIN_VALUES = 4,           /* RemoveInstanceTypeOptionsByPriceAndMinValues fails: the cheaper options miss minValues */
+       KP_UNCONS_NOT_CHEAPER = 5,          /* no option with WorstLaunchPrice < candidate price */
+       KP_UNCONS_SPOT_TO_SPOT_TOO_FEW = 6, /* single-node spot-to-spot: fewer than 15 cheaper options */
+       KP_UNCONS_SAME_INSTANCE_TYPE = 7 }; /* multi-node: REPLACE, but filterOutSameInstanceType left nothing (valid == 0) */
+enum { KP_UNCONS_F_UNINITIALIZED_NODE = 1, /* a non-pending pod landed on an uninitialized node */
+       KP_UNCONS_F_TRUNCATED = 2,          /* TruncateInstanceTypes dropped the NodeClaim (minValues over its first max_instance_types) */
+       KP_UNCONS_F_SPOT_TO_SPOT = 4 };     /* the decision went through computeSpotToSpotConsolidation */
+typedef struct kp_probe_explanation {
+    int32_t reason, flags;
+    int32_t n_unscheduled;     /* PODS_UNSCHEDULABLE: non-pending pods without a place at the probe's end; with F_TRUNCATED
+                                  plus the dropped NodeClaim's non-pending pods; else 0 */
+    int32_t first_unscheduled; /* index into cluster.pods of the first such placeless pod in queue order (the Solve's
+                                  queue: the pod with the smallest position in it), -1 when there is none (the pods of a
+                                  dropped NodeClaim are counted, not listed) */
+    int32_t n_options;         /* options of the one new NodeClaim after TruncateInstanceTypes, 0 when there is none (no
+                                  NodeClaim, a second one, a dropped one, or pods left unscheduled) */
+    int32_t n_cheaper;         /* of those: WorstLaunchPrice < candidate price (spot-narrowed when F_SPOT_TO_SPOT), counted
+                                  before the minValues check and before the cut to 15 */
+    int32_t min_needed;        /* spot-to-spot with minValues: minNeeded (0 where the minValues check itself fails), else 0 */
+    int32_t pad;
+    double candidate_price;
+    double cheapest_price;     /* lowest WorstLaunchPrice among the n_options (same narrowing), 0 when n_options == 0 */
+} kp_probe_explanation;
+
+/* rows[i] explains probe probe_begin + i of `mode` (KP_CONSOLIDATE_SINGLE or _MULTI; the range as for
+ * kp_consolidate_execute, probe_end <= 0: to the end).  Needs a prepared pass only (KP_E_STATE without one) and stays
+ * valid until the ctx's next prepare, catalog upload or availability patch.  KP_E_BUFFER when cap_rows is smaller than the
+ * range (nothing is launched).  Every probe of the range is re-run on the primary device by a variant of the probe kernel
+ * that records its decision tail; the call writes nothing the pass keeps: every later kp_consolidate_execute,
+ * kp_consolidate_command and kp_consolidate_replacement returns what it would have returned, a command that would have
+ * replayed a full pass still replays it, and kp_consolidate_stats is unchanged.  (The one thing it shares with the pass is
+ * the device prep of the prepared cluster — queue order, class / template / existing-node masks — which whichever call runs
+ * first after the prepare computes and later calls reuse; the prep time kp_consolidate_stats reports is that of the last
+ * kp_consolidate_execute, near zero when an explain call already did the work.) */
+kp_status kp_consolidate_explain(kp_ctx* ctx, int32_t mode, int32_t probe_begin, int32_t probe_end,
+                                 kp_probe_explanation* rows, int32_t cap_rows);
+/* The pods behind one KP_UNCONS_PODS_UNSCHEDULABLE probe: for the first max_pods (<= 0: all) non-pending pods left
+ * without a place, in queue order, one kp_pod_explanation per NodePool in template order, with the fields and meanings
+ * of kp_solve_explain.  A probe with any other reason: KP_OK and *needed == 0.  *needed receives the row count,
+ * KP_E_BUFFER when cap is smaller.  A pod is diagnosed at its final relaxation stage inside that probe, against the
+ * probe's own remaining NodePool limits (the prepared limits, plus the candidates' returned capacity, minus subtractMax
+ * of its NodeClaim).  `key` is resolved by kp_consolidate_explain_key.  Rows follow kp_solve_explain's "never guessed"
+ * rule: a pod whose final class is constrained by a topology group, in a pass that has groups, gets KP_WHY_UNKNOWN with
+ * every other field 0 / -1 (the probe's topology counts live in its own ProbeTopo, which the explain kernel cannot
+ * read), and the reservation residual is KP_WHY_UNKNOWN too (the probe's reservation capacities are not kept;
+ * KP_WHY_RESERVED never appears here).  A probe with KP_UNCONS_F_TRUNCATED lists the pods its queue still held, if any;
+ * the dropped NodeClaim's pods are counted in n_unscheduled and not listed. */
+kp_status kp_consolidate_explain_pods(kp_ctx* ctx, int32_t mode, int32_t probe, int32_t max_pods,
+                                      kp_pod_explanation* rows, int64_t cap, int64_t* needed);
+/* Name of key `key` of the prepared pass's key table (valid as long as kp_consolidate_explain is); as
+ * kp_solve_explain_key. */
+kp_status kp_consolidate_explain_key(kp_ctx* ctx, int32_t key, char* buf, int64_t cap, int64_t* needed);
+/* The last kp_consolidate_explain / kp_consolidate_explain_pods: ms[0] device time of its kernels (HIP events), ms[1]
+ * the whole call; counters[0] probes explained, [1] (shape, NodePool) pairs diagnosed.  n_counters up to 2. */
+kp_status kp_consolidate_explain_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters);
+
 #ifdef __cplusplus
 }
 #endif

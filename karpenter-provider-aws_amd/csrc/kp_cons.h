@@ -131,3 +131,20 @@ struct KpCons {
     int32_t* vov_cnt;           // [FULL workers][vov_cap][VD]
     uint64_t* vov_mask;         // [FULL workers][vov_cap][VW]
 };
+
+// Operands of consolidate_explain_kernel (kp_consolidate_explain): the extra kernel argument of that entry alone; KpCons
+// and the arguments of every other kernel are as above.  rows[output index] receives why the probe ended as it did.
+// pods != null (kp_consolidate_explain_pods: one probe per launch, like KpCons::rec_i): the probe's placeless non-pending
+// pods in the order the queue holds them at its end, each with its queue position (the host orders them by it), its final
+// relaxation class and shape, and the probe's remaining NodePool limits when its queue ended.
+struct KpConsExplain {
+    kp_probe_explanation* rows;  // [n_probes]
+    int32_t* pods;               // [cap_pods]
+    int32_t* pod_rank;           // [cap_pods]
+    int32_t* pod_cls;            // [cap_pods]
+    int32_t* pod_shape;          // [cap_pods]
+    int32_t* n_rec;              // [1] pods recorded (a probe stopped at its second NodeClaim records none: preset 0)
+    int32_t cap_pods;
+    int32_t pad;
+    int64_t* rem;                // [NT][R]
+};

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include <cfloat>
+#include <type_traits>
 
 #include "kp_cons.h"
 #include "kp_device.h"
@@ -207,9 +208,22 @@ __device__ inline uint64_t commit_held(int32_t* rcap, uint64_t old, const WaveSc
 // DevT / ConsT: KpDev / KpCons by value (the fast variant: its kernel arguments) or const references to the FULL
 // variant's device copies — a by-value copy of those, indexed dynamically (active_axes ...), went to scratch per lane
 // (1.3 KB per lane, 87 MB of scratch writes per replace-leg launch).
+// consolidate_body's explain operands and per-probe explain state: empty outside the XPL instantiation
+struct NoExplain {};
+template <bool XPL>
+struct XplState {};
+template <>
+struct XplState<true> {
+    int nuns = 0, first = -1, reason = KP_UNCONS_NONE, flags = 0, nopt = 0, ncheap = 0, need = 0;
+    bool uninit = false;  // a non-pending pod landed on an uninitialized node (`bad` has other causes too)
+    double cheapest = 0.0;
+};
+// XPL (XplT = KpConsExplain; FULL, MUT instantiation only): consolidate_explain_kernel — the probe also records why it
+// ended as it did (x: the test of computeConsolidation's tail that decided, and on request the pods left without a place).
 template <bool FULL, bool RESV = false, bool TOPO = false, int NA = 0, bool MUT = false, class DevT = KpDev,
-          class ConsT = KpCons>
-__device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
+          class ConsT = KpCons, class XplT = NoExplain>
+__device__ __forceinline__ void consolidate_body(DevT d, ConsT k, XplT x = XplT{}) {
+    constexpr bool XPL = !std::is_same<XplT, NoExplain>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     ConsShared& S = *reinterpret_cast<ConsShared*>(smem);
     ReqHdr* nch = reinterpret_cast<ReqHdr*>(smem + k.off_hdr);
@@ -330,7 +344,7 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
         for (int w = lane; w < EW; w += 64) {
             excl[w] = 0;
             modb[w] = 0;
-            if (MUT) mutn[w] = 0;
+            if (MUT && (!XPL || k.mut)) mutn[w] = 0;  // (XPL also runs passes without MUT probes: no mutn in their LDS plan)
         }
         // a MUT probe reschedules a mutator's pod: the fast variants hand it over, the MUT variant runs it serially
         const bool mutp = k.mut && __builtin_amdgcn_readfirstlane(single ? k.mut_s[gp] : k.mut_m[gp]) != 0;
@@ -522,6 +536,7 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
 #pragma unroll
         for (int ai = 0; ai < KP_LDS_AXES; ai++) ch[ai] = cd[ai] = 0;
         bool bad = false, stop = false;
+        XplState<XPL> xst;
         uint64_t nc_opts = 0;
         uint64_t nc_held = 0;  // RESV: lane r: word r of the reservations the in-flight NodeClaim holds
         // Largest headroom of the cached chunk's nodes that are not candidates (lanes past E hold 0): the chunk's entry
@@ -947,6 +962,7 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                         const uint64_t npl = took & ~pendm;
                         if ((iw >> jn) & 1ull) ok_np += __popcll(npl);
                         else if (npl) bad = true;
+                        if constexpr (XPL) xst.uninit = xst.uninit || (npl && !((iw >> jn) & 1ull));
                     }
                     if ((touched >> lane) & 1ull) {  // each lane writes back its own node
                         AXL(ai) hs[(w * AA + ai) * 64 + lane] = hl[ai];
@@ -991,6 +1007,7 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                     if (!pend) {
                         if ((cinit >> (jf & 63)) & 1ull) ok_np++;
                         else bad = true;
+                        if constexpr (XPL) xst.uninit = xst.uninit || !((cinit >> (jf & 63)) & 1ull);
                     }
                 }
                 if (prof) pf_miss_cyc += __builtin_amdgcn_s_memtime() - cm0;
@@ -1128,6 +1145,7 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                 if (!pend) {
                     if ((cinit >> (jf & 63)) & 1ull) ok_np++;
                     else bad = true;  // SimulateScheduling: uninitialized-node placement is an error
+                    if constexpr (XPL) xst.uninit = xst.uninit || !((cinit >> (jf & 63)) & 1ull);
                 }
                 continue;
             }
@@ -1306,6 +1324,45 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
 
+        // XPL: the non-pending pods the queue still holds (a queue cycle without progress): how many, the first in queue
+        // order, and on request each one with its queue position, final class and shape, and the probe's limits
+        if constexpr (XPL) {
+            if (!stop) {
+                uint64_t best = ~0ull;  // (queue position, pod) of the first placeless pod
+                for (int b = 0; b < count; b += 64) {
+                    const int pos = head + b + lane;
+                    const bool in = b + lane < count;
+                    const int slot = pos % cap;
+                    const int ent = in ? ld32(&ring[slot]) : -1;
+                    const bool np = in && ent >= 0;
+                    const int p = ent & 0x3fffffff;
+                    const int rk = np ? k.rank[p] : 0;
+                    const uint64_t m = ballot(np);
+                    if (np) {
+                        const uint64_t key = ((uint64_t)(uint32_t)rk << 32) | (uint32_t)p;
+                        best = key < best ? key : best;
+                        const int at = xst.nuns + __popcll(m & ((1ull << lane) - 1ull));
+                        if (x.pods && at < x.cap_pods) {
+                            const bool rel = (ent & 0x40000000) != 0;
+                            x.pods[at] = p;
+                            x.pod_rank[at] = rk;
+                            x.pod_cls[at] = rel ? (ld32(&rcls[slot]) & 0x7fffffff) : pcls[p];
+                            x.pod_shape[at] = rel ? ld32(&rshape[slot]) : pshape[p];
+                        }
+                    }
+                    xst.nuns += __popcll(m);
+                }
+                for (int o = 32; o >= 1; o >>= 1) {
+                    const uint64_t y = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), o) << 32) |
+                                       (uint32_t)__shfl_xor((int)(uint32_t)best, o);
+                    best = y < best ? y : best;
+                }
+                if (xst.nuns > 0) xst.first = (int)(uint32_t)best;
+                if (x.pods && lane == 0) x.n_rec[0] = xst.nuns < x.cap_pods ? xst.nuns : x.cap_pods;
+            }
+            if (x.rem)
+                for (int i = lane; i < NT * R; i += 64) x.rem[i] = rem[i];
+        }
         if (!FULL && aborted) {
             if (lane == 0) {
                 const int slot = atomicAdd(&k.next_probe[2], 1);
@@ -1318,10 +1375,26 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
         double rprice = 0.0;
         bool truncated_out = false;  // the NodeClaim failed TruncateInstanceTypes' minValues check
         const bool all = !stop && !bad && ok_np == n_np;
+        // XPL: the test that ends the probe, in computeConsolidation's order (the second NodeClaim first: the probe
+        // stopped there)
+        if constexpr (XPL) {
+            if (stop) {
+                xst.reason = KP_UNCONS_MULTIPLE_NODECLAIMS;
+                xst.nuns = 0;
+                xst.first = -1;
+            } else if (!all) {
+                xst.reason = KP_UNCONS_PODS_UNSCHEDULABLE;
+                if (xst.uninit) xst.flags |= KP_UNCONS_F_UNINITIALIZED_NODE;
+            } else {
+                xst.nuns = 0;  // (pending pods only)
+                xst.first = -1;
+            }
+        }
         if (all && n_nc == 0) {
             decision = KP_DECISION_DELETE;
             valid = 1;
-        } else if (FULL && all) {
+        } else if (FULL && (all || (XPL && !stop && n_nc == 1))) {
+            // (XPL: a probe that left pods unscheduled still learns whether TruncateInstanceTypes drops its NodeClaim)
             // FinalizeScheduling: a NodeClaim holding reservations gets reservation-id In [held IDs]
             if (RESV && ballot(nc_held != 0) && d.key_resvid >= 0) {
                 if (lane == 0) {
@@ -1478,9 +1551,29 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                 // scheduled (NONE); otherwise no new NodeClaim is left and the candidates' pods all landed: DELETE
                 none = true;
                 truncated_out = true;
+                if constexpr (XPL) {
+                    xst.flags |= KP_UNCONS_F_TRUNCATED;
+                    if (nc_nonpend > 0) {
+                        xst.reason = KP_UNCONS_PODS_UNSCHEDULABLE;
+                        xst.nuns += nc_nonpend;
+                    }
+                    // pods were left unscheduled anyway: the probe's row stays what the other variants write for it
+                    // (NONE, its one NodeClaim counted)
+                    if (!all) truncated_out = false;
+                }
+            } else if (XPL && !all) {
+                none = true;
             } else if (all_spot && has_spot) {  // computeSpotToSpotConsolidation
+                if constexpr (XPL) {
+                    const double wp = my_t >= 0 ? worst_launch_price(d, k, my_t, mt & k.spot_slots) : DBL_MAX;
+                    xst.flags |= KP_UNCONS_F_SPOT_TO_SPOT;
+                    xst.nopt = nsel;
+                    xst.ncheap = __popcll(ballot(my_t >= 0 && wp < cprice));
+                    xst.cheapest = wave_min_f64(wp);
+                }
                 if (!k.spot_to_spot) {
                     none = true;
+                    if constexpr (XPL) xst.reason = KP_UNCONS_SPOT_TO_SPOT_DISABLED;
                 } else {
                     spot_only = true;  // Requirements.Add(capacity-type In [spot])
                     keep = my_t >= 0 && worst_launch_price(d, k, my_t, mt & k.spot_slots) < cprice;
@@ -1488,19 +1581,37 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                     int need = 0;
                     if (has_min && !min_values_ok(d, nch, nc_tmpl, my_t, km, lane, &need)) {
                         none = true;  // RemoveInstanceTypeOptionsByPriceAndMinValues keeps minValues
+                        if constexpr (XPL) xst.reason = KP_UNCONS_MIN_VALUES;
                     } else if (!km) {
                         none = true;
+                        if constexpr (XPL) xst.reason = KP_UNCONS_NOT_CHEAPER;
                     } else if (c1 - c0 == 1) {
                         // MinInstanceTypesForSpotToSpotConsolidation; the kept list is cut to max(15, minNeeded)
                         const int cut = has_min && need > 15 ? need : 15;
                         if (__popcll(km) < 15) none = true;
                         else keep = keep && __popcll(km & ((1ull << lane) - 1)) < cut;
+                        if constexpr (XPL)
+                            if (none) xst.reason = KP_UNCONS_SPOT_TO_SPOT_TOO_FEW;
                     }
+                    if constexpr (XPL) xst.need = (has_min && xst.reason != KP_UNCONS_MIN_VALUES) ? need : 0;
                 }
             } else {  // RemoveInstanceTypeOptionsByPriceAndMinValues
                 keep = my_t >= 0 && worst_launch_price(d, k, my_t, mt, mr, mrw) < cprice;
                 const uint64_t km = ballot(keep);
+                if constexpr (XPL) {  // minValues is tested before "no cheaper option", as in the spot-to-spot branch
+                    xst.nopt = nsel;
+                    xst.ncheap = __popcll(km);
+                    xst.cheapest = wave_min_f64(my_t >= 0 ? worst_launch_price(d, k, my_t, mt, mr, mrw) : DBL_MAX);
+                    if (has_min && !min_values_ok(d, nch, nc_tmpl, my_t, km, lane, nullptr)) {
+                        none = true;
+                        xst.reason = KP_UNCONS_MIN_VALUES;
+                    } else if (!km) {
+                        none = true;
+                        xst.reason = KP_UNCONS_NOT_CHEAPER;
+                    }
+                } else {
                 if (!km || (has_min && !min_values_ok(d, nch, nc_tmpl, my_t, km, lane, nullptr))) none = true;
+                }
                 spot_only = has_spot && has_od;  // spot/on-demand flexible replacement narrowed to spot
             }
             if (truncated_out && nc_nonpend == 0) {
@@ -1520,6 +1631,8 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
                 }
                 const uint64_t km = ballot(keep);
                 valid = km != 0;
+                if constexpr (XPL)
+                    if (!valid) xst.reason = KP_UNCONS_SAME_INSTANCE_TYPE;
                 nrep = __popcll(km);
                 rprice = nrep ? wave_min_f64(keep ? wl : DBL_MAX) : 0.0;
                 if (FULL && k.rec_i) {  // kp_consolidate_command: the replacement NodeClaim of this probe
@@ -1549,6 +1662,20 @@ __device__ __forceinline__ void consolidate_body(DevT d, ConsT k) {
             o.candidate_price = cprice;
             o.replacement_price = rprice;
             k.out[oi] = o;
+            if constexpr (XPL) {
+                kp_probe_explanation e;
+                e.reason = xst.reason;
+                e.flags = xst.flags;
+                e.n_unscheduled = xst.nuns;
+                e.first_unscheduled = xst.first;
+                e.n_options = xst.nopt;
+                e.n_cheaper = xst.ncheap;
+                e.min_needed = xst.need;
+                e.pad = 0;
+                e.candidate_price = cprice;
+                e.cheapest_price = xst.cheapest;
+                x.rows[oi] = e;
+            }
             // counters stay in LDS until the worker exits (per-probe global atomics on 16 words serialise in L2)
             S.st[CS_POPS] += st_pops;
             S.st[CS_EX_NODES] += st_nodes;
@@ -1607,6 +1734,14 @@ template <bool RESV, bool TOPO, bool MUT = false>
 __global__ __launch_bounds__(64) void consolidate_full_kernel(const KpDev* __restrict__ dp, const KpCons* __restrict__ kp) {
     if (kp->no_fast != 1 && ld32(&kp->next_probe[2]) == 0) return;
     consolidate_body<true, RESV, TOPO, 0, MUT, const KpDev&, const KpCons&>(*dp, *kp);
+}
+
+// kp_consolidate_explain's entry: every probe of the list on the FULL path's MUT instantiation (the serial superset: a
+// probe that reschedules no mutator's pod runs the window pass as in the other FULL instantiations) with XPL on.
+template <bool RESV, bool TOPO>
+__global__ __launch_bounds__(64) void consolidate_explain_kernel(const KpDev* __restrict__ dp, const KpCons* __restrict__ kp,
+                                                                  KpConsExplain x) {
+    consolidate_body<true, RESV, TOPO, 0, true, const KpDev&, const KpCons&, KpConsExplain>(*dp, *kp, x);
 }
 
 // cmax0[w][ai]: the largest headroom on active axis ai over the nodes of chunk w (one wave per chunk; lanes past E and
@@ -1700,7 +1835,9 @@ hipError_t kp_cons_set_attributes() {
                          (const void*)consolidate_full_kernel<true, false>, (const void*)consolidate_kernel<false, false, true>,
                          (const void*)consolidate_full_kernel<false, true>, (const void*)consolidate_full_kernel<true, true>,
                          (const void*)consolidate_full_kernel<false, false, true>, (const void*)consolidate_full_kernel<true, false, true>,
-                         (const void*)consolidate_full_kernel<false, true, true>, (const void*)consolidate_full_kernel<true, true, true>};
+                         (const void*)consolidate_full_kernel<false, true, true>, (const void*)consolidate_full_kernel<true, true, true>,
+                         (const void*)consolidate_explain_kernel<false, false>, (const void*)consolidate_explain_kernel<true, false>,
+                         (const void*)consolidate_explain_kernel<false, true>, (const void*)consolidate_explain_kernel<true, true>};
     for (const void* f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS_BYTES);
         if (e != hipSuccess) return e;
@@ -1751,6 +1888,22 @@ hipError_t kp_launch_consolidate(const KpDev& d, const KpCons& k, int n_workers,
         } else {
             hipLaunchKernelGGL((consolidate_full_kernel<false, false>), gf, dim3(64), lds, s, d_dev, d_k);
         }
+    }
+    return hipGetLastError();
+}
+
+// kp_consolidate_explain: every probe of k (no_fast == 1: the work counter) on consolidate_explain_kernel.
+hipError_t kp_launch_consolidate_explain(const KpDev& d, const KpCons& k, const KpConsExplain& x, int n_workers,
+                                         hipStream_t s, KpDev* d_dev, KpCons* d_k) {
+    if (n_workers <= 0 || k.n_probes <= 0) return hipSuccess;
+    const size_t lds = (size_t)k.lds_bytes;
+    const dim3 gf(n_workers < KP_CONS_FULL_WORKERS ? n_workers : KP_CONS_FULL_WORKERS);
+    if (k.G > 0) {
+        if (d.ro) hipLaunchKernelGGL((consolidate_explain_kernel<true, true>), gf, dim3(64), lds, s, d_dev, d_k, x);
+        else hipLaunchKernelGGL((consolidate_explain_kernel<false, true>), gf, dim3(64), lds, s, d_dev, d_k, x);
+    } else {
+        if (d.ro) hipLaunchKernelGGL((consolidate_explain_kernel<true, false>), gf, dim3(64), lds, s, d_dev, d_k, x);
+        else hipLaunchKernelGGL((consolidate_explain_kernel<false, false>), gf, dim3(64), lds, s, d_dev, d_k, x);
     }
     return hipGetLastError();
 }

@@ -619,6 +619,18 @@ struct kp_ctx {
     hipEvent_t xev[2] = {};
     double explain_ms[2] = {};
     int64_t explain_counts[3] = {};
+    // kp_consolidate_explain: valid from kp_consolidate_prepare until a prepare, catalog upload or availability patch;
+    // staging buffers of its own (nothing the pass or kp_solve_explain caches is touched), events, the last call's figures
+    bool cx_ok = false;
+    DBuf<kp_probe_explanation> d_cx_rows;
+    DBuf<int32_t> d_cx_pods, d_cx_rank, d_cx_cls, d_cx_shape, d_cx_pcls, d_cx_rep, d_cx_nrec;
+    DBuf<int64_t> d_cx_rem;
+    DBuf<uint64_t> d_cx_tol;
+    DBuf<uint8_t> d_cx_hblock;
+    DBuf<KpExplainRow> d_cx_xrows;
+    hipEvent_t cxev[4] = {};
+    double cx_ms[2] = {};
+    int64_t cx_counts[2] = {};
 };
 
 static kp_status fail(kp_ctx* c, kp_status st, const std::string& msg) {
@@ -727,6 +739,8 @@ extern "C" kp_status kp_ctx_destroy(kp_ctx* ctx) {
     for (auto& e : ctx->lev)
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->xev)
+        if (e) hipEventDestroy(e);
+    for (auto& e : ctx->cxev)
         if (e) hipEventDestroy(e);
     if (ctx->lstream2) {
         hipStreamSynchronize(ctx->lstream2);
@@ -1216,6 +1230,7 @@ static kp_status patch_avail_one(kp_ctx* ctx, const uint8_t* available, int32_t 
     if (n != (int)ctx->off_type.size()) return fail(ctx, KP_E_INVALID, "offering count mismatch");
     HIPCHK(hipSetDevice(ctx->device));
     ctx->explain_ok = false;  // an explanation reads the availability the Solve ran with
+    ctx->cx_ok = false;
     rebuild_avail(ctx, std::vector<uint8_t>(available, available + n));
     HIPCHK(ctx->d_avail_zc.upload(ctx->avail_zc, ctx->stream));
     std::fill(ctx->ro_avail.begin(), ctx->ro_avail.end(), 0ull);
@@ -3944,6 +3959,35 @@ static uint64_t explain_born(const kp_ctx* c, const std::vector<int32_t>& final_
     return born;
 }
 
+// The key a row names: the failing key with the smallest name (kmask: class keys of the shape's class / entries of the
+// template's min_keys), from the prepared solve's key tables on the device.
+struct ExplainKeys {
+    std::vector<int32_t> koff, ckeys, mkeys;
+    kp_status load(kp_ctx* ctx) {
+        const kp_ctx* c = ctx;
+        koff.resize(c->C + c->NT + 1);
+        HIPCHK(hipMemcpy(koff.data(), c->d_cls_koff.p, koff.size() * 4, hipMemcpyDeviceToHost));
+        ckeys.resize(std::max(koff.back(), 1));
+        if (koff.back() > 0) HIPCHK(hipMemcpy(ckeys.data(), c->d_cls_keys.p, (size_t)koff.back() * 4, hipMemcpyDeviceToHost));
+        mkeys.resize((size_t)c->NT * KP_MAX_CLASS_KEYS);
+        HIPCHK(hipMemcpy(mkeys.data(), c->d_min_keys.p, mkeys.size() * 4, hipMemcpyDeviceToHost));
+        return KP_OK;
+    }
+    int key_of(const kp_ctx* c, const KpExplainRow& r, int cls, int j) const {
+        int best = -1;
+        for (uint32_t m = r.kmask; m; m &= m - 1) {
+            const int i = __builtin_ctz(m);
+            const int k = r.reason == KPX_MIN_VALUES ? mkeys[(size_t)j * KP_MAX_CLASS_KEYS + i] : ckeys[koff[cls] + i];
+            if (k >= 0 && (best < 0 || c->sol.keys[k].name < c->sol.keys[best].name)) best = k;
+        }
+        // the hostname requirement is no class key (the Solve folds it into the toleration mask): it fails too
+        const int hk = c->x_host_key;
+        if (r.reason == KPX_REQUIREMENTS && r.hostkey && hk >= 0 && (best < 0 || c->sol.keys[hk].name < c->sol.keys[best].name))
+            best = hk;
+        return best;
+    }
+};
+
 extern "C" kp_status kp_solve_explain(kp_ctx* ctx, int32_t n_pods, const int32_t* pods, kp_pod_explanation* out,
                                       int64_t cap, int64_t* needed) try {
     if (!ctx || !needed || (pods && n_pods < 0)) return KP_E_INVALID;
@@ -4029,31 +4073,11 @@ extern "C" kp_status kp_solve_explain(kp_ctx* ctx, int32_t n_pods, const int32_t
     HIPCHK(hipStreamSynchronize(s));
     float kms = 0;
     HIPCHK(hipEventElapsedTime(&kms, c->xev[0], c->xev[1]));
-    // the failing key with the smallest name (kmask: class keys of the shape's class / entries of the template's min_keys)
-    std::vector<int32_t> koff, ckeys, mkeys;
-    auto key_of = [&](const KpExplainRow& r, int cls, int j) -> int {
-        int best = -1;
-        for (uint32_t m = r.kmask; m; m &= m - 1) {
-            const int i = __builtin_ctz(m);
-            const int k = r.reason == KPX_MIN_VALUES ? mkeys[(size_t)j * KP_MAX_CLASS_KEYS + i] : ckeys[koff[cls] + i];
-            if (k >= 0 && (best < 0 || c->sol.keys[k].name < c->sol.keys[best].name)) best = k;
-        }
-        // the hostname requirement is no class key (the Solve folds it into the toleration mask): it fails too
-        const int hk = c->x_host_key;
-        if (r.reason == KPX_REQUIREMENTS && r.hostkey && hk >= 0 && (best < 0 || c->sol.keys[hk].name < c->sol.keys[best].name))
-            best = hk;
-        return best;
-    };
+    ExplainKeys keys;
     bool need_keys = false;
     for (const KpExplainRow& r : rows) need_keys |= r.kmask != 0;  // (a hostname-only failure needs no table)
-    if (need_keys) {
-        koff.resize(c->C + NT + 1);
-        HIPCHK(hipMemcpy(koff.data(), c->d_cls_koff.p, koff.size() * 4, hipMemcpyDeviceToHost));
-        ckeys.resize(std::max(koff.back(), 1));
-        if (koff.back() > 0) HIPCHK(hipMemcpy(ckeys.data(), c->d_cls_keys.p, (size_t)koff.back() * 4, hipMemcpyDeviceToHost));
-        mkeys.resize((size_t)NT * KP_MAX_CLASS_KEYS);
-        HIPCHK(hipMemcpy(mkeys.data(), c->d_min_keys.p, mkeys.size() * 4, hipMemcpyDeviceToHost));
-    }
+    if (need_keys)
+        if (const kp_status st = keys.load(ctx); st != KP_OK) return st;
     for (size_t i = 0; i < list.size(); i++)
         for (int j = 0; j < NT; j++) {
             static const KpExplainRow none{};  // KPX_UNKNOWN
@@ -4062,7 +4086,7 @@ extern "C" kp_status kp_solve_explain(kp_ctx* ctx, int32_t n_pods, const int32_t
             o.pod = list[i];
             o.nodepool = c->tmpl_np[j];
             o.reason = r.reason;
-            o.key = (r.kmask || r.hostkey) ? key_of(r, pcls[rep[of_pod[i]]], j) : -1;
+            o.key = (r.kmask || r.hostkey) ? keys.key_of(c, r, pcls[rep[of_pod[i]]], j) : -1;
             o.criteria = r.criteria;
             o.n_options = r.n_options;
             o.n_requirements = r.n_requirements;
@@ -4268,6 +4292,7 @@ static kp_status cons_prepare_one(kp_ctx* ctx, const kp_consolidate_input* in) t
     if (!ctx || !in) return KP_E_INVALID;
     ctx->cons_prepared = false;
     ctx->cons_prep_valid = false;
+    ctx->cx_ok = false;
     ctx->cons_gen++;  // cached pass rows and read-backs of kp_consolidate_command are stale
     if (ctx->has_reserved && !ctx->ro_ok)
         return fail(ctx, KP_E_UNSUPPORTED, "consolidation over this catalog: " + ctx->ro_why);
@@ -4371,6 +4396,7 @@ static kp_status cons_prepare_one(kp_ctx* ctx, const kp_consolidate_input* in) t
     HIPCHK(c->d_cons_stats.ensure(CS_COUNT));
     HIPCHK(hipStreamSynchronize(s));
     c->cons_prepared = true;
+    c->cx_ok = true;
     c->n_pass_launches = c->n_readbacks = 0;
     return KP_OK;
 } catch (const std::exception& e) {
@@ -4394,9 +4420,9 @@ static int cons_probes(const kp_ctx* c, int mode) {
 // One device's share of a pass: multi-node probes [m0, m1) and single-node probes [s0, s1) of the prepared pass in one
 // launch (the multi-node prefixes first, longest first), results into out_multi[m1 - m0] / out_single[s1 - s0].
 // record: kp_consolidate_command's read-back run of one probe (FULL variant only; the replacement NodeClaim lands in
-// d_rec_*).
+// d_rec_*).  xp: kp_consolidate_explain's run of the probes on consolidate_explain_kernel (FULL path only), its operands.
 static kp_status cons_run(kp_ctx* ctx, int m0, int m1, int s0, int s1, kp_probe_result* out_multi,
-                          kp_probe_result* out_single, bool record = false) try {
+                          kp_probe_result* out_single, bool record = false, const KpConsExplain* xp = nullptr) try {
     if (!ctx) return KP_E_INVALID;
     if (!ctx->cons_prepared || !ctx->have_catalog)
         return fail(ctx, KP_E_STATE, "kp_consolidate_execute before kp_consolidate_prepare");
@@ -4573,11 +4599,18 @@ static kp_status cons_run(kp_ctx* ctx, int m0, int m1, int s0, int s1, kp_probe_
         k.rec_words = c->d_rec_words.p;
         k.no_fast = 1;
     }
+    if (xp) k.no_fast = 1;
     HIPCHK(c->d_cons_dev.ensure(1));
     HIPCHK(c->d_cons_k.ensure(1));
     HIPCHK(hipMemcpyAsync(c->d_cons_dev.p, &d, sizeof(KpDev), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_cons_k.p, &k, sizeof(KpCons), hipMemcpyHostToDevice, s));
-    HIPCHK(kp_launch_consolidate(d, k, workers, s, c->d_cons_dev.p, c->d_cons_k.p));
+    if (xp) {
+        HIPCHK(hipEventRecord(c->cxev[0], s));
+        HIPCHK(kp_launch_consolidate_explain(d, k, *xp, workers, s, c->d_cons_dev.p, c->d_cons_k.p));
+        HIPCHK(hipEventRecord(c->cxev[1], s));
+    } else {
+        HIPCHK(kp_launch_consolidate(d, k, workers, s, c->d_cons_dev.p, c->d_cons_k.p));
+    }
     HIPCHK(hipEventRecord(c->ev[2], s));
     if (nmp)
         HIPCHK(hipMemcpyAsync(out_multi, c->d_probe_out.p, (size_t)nmp * sizeof(kp_probe_result), hipMemcpyDeviceToHost, s));
@@ -4905,6 +4938,235 @@ extern "C" kp_status kp_consolidate_replacement(kp_ctx* ctx, int32_t mode, int32
     return cons_readback(ctx, mode, probe, out);
 } catch (const std::exception& e) {
     return fail(ctx, KP_E_INVALID, e.what());
+}
+
+// ---- kp_consolidate_explain: the probes of a range re-run on consolidate_explain_kernel (primary device) ----
+static bool cons_explainable(const kp_ctx* ctx) {
+    return ctx->cons_prepared && ctx->have_catalog && ctx->cx_ok;
+}
+
+// One explain run of probes [b0, b1) of `mode` with operands x: the pass's timings and counters stay those of the pass
+// (as in cons_readback), the device time of the run goes to *kms.
+static kp_status cons_explain_run(kp_ctx* ctx, int mode, int b0, int b1, const KpConsExplain& x, float* kms) {
+    for (auto& e : ctx->cxev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    double ms_keep[3];
+    int64_t st_keep[CS_COUNT];
+    memcpy(ms_keep, ctx->cons_ms, sizeof ms_keep);
+    memcpy(st_keep, ctx->cons_stats, sizeof st_keep);
+    std::vector<kp_probe_result> rows(std::max(1, b1 - b0));
+    const bool multi = mode == KP_CONSOLIDATE_MULTI;
+    const kp_status st = multi ? cons_run(ctx, b0, b1, 0, 0, rows.data(), nullptr, false, &x)
+                               : cons_run(ctx, 0, 0, b0, b1, nullptr, rows.data(), false, &x);
+    memcpy(ctx->cons_ms, ms_keep, sizeof ms_keep);
+    memcpy(ctx->cons_stats, st_keep, sizeof st_keep);
+    if (st != KP_OK) return st;
+    HIPCHK(hipEventElapsedTime(kms, ctx->cxev[0], ctx->cxev[1]));
+    return KP_OK;
+}
+
+extern "C" kp_status kp_consolidate_explain(kp_ctx* ctx, int32_t mode, int32_t probe_begin, int32_t probe_end,
+                                            kp_probe_explanation* rows, int32_t cap_rows) try {
+    if (!ctx) return KP_E_INVALID;
+    if (mode != KP_CONSOLIDATE_SINGLE && mode != KP_CONSOLIDATE_MULTI)
+        return fail(ctx, KP_E_INVALID, "kp_consolidate_explain: mode must be SINGLE or MULTI");
+    if (!cons_explainable(ctx))
+        return fail(ctx, KP_E_STATE, "kp_consolidate_explain needs a prepared pass (none since the last prepare, catalog "
+                                     "upload or availability patch)");
+    const auto t0 = clk::now();
+    const int np = cons_probes(ctx, mode);
+    const int b0 = probe_begin > 0 ? probe_begin : 0;
+    const int b1 = probe_end > 0 && probe_end < np ? probe_end : np;
+    if (b0 > b1) return fail(ctx, KP_E_INVALID, "probe range outside the probe list");
+    const int n = b1 - b0;
+    ctx->cx_ms[0] = ctx->cx_ms[1] = 0;
+    ctx->cx_counts[0] = ctx->cx_counts[1] = 0;
+    if (n > cap_rows || (n > 0 && !rows)) return fail(ctx, KP_E_BUFFER, "kp_consolidate_explain: " + std::to_string(n) + " rows");
+    if (n == 0) return KP_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(ctx->d_cx_rows.ensure(n));
+    KpConsExplain x{};
+    x.rows = ctx->d_cx_rows.p;
+    float kms = 0;
+    if (const kp_status st = cons_explain_run(ctx, mode, b0, b1, x, &kms); st != KP_OK) return st;
+    HIPCHK(hipMemcpy(rows, ctx->d_cx_rows.p, (size_t)n * sizeof(kp_probe_explanation), hipMemcpyDeviceToHost));
+    ctx->cx_ms[0] = kms;
+    ctx->cx_ms[1] = ns_since(t0) * 1e-6;
+    ctx->cx_counts[0] = n;
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_consolidate_explain_pods(kp_ctx* ctx, int32_t mode, int32_t probe, int32_t max_pods,
+                                                 kp_pod_explanation* out, int64_t cap, int64_t* needed) try {
+    if (!ctx || !needed) return KP_E_INVALID;
+    if (mode != KP_CONSOLIDATE_SINGLE && mode != KP_CONSOLIDATE_MULTI)
+        return fail(ctx, KP_E_INVALID, "kp_consolidate_explain_pods: mode must be SINGLE or MULTI");
+    if (!cons_explainable(ctx))
+        return fail(ctx, KP_E_STATE, "kp_consolidate_explain_pods needs a prepared pass (none since the last prepare, "
+                                     "catalog upload or availability patch)");
+    if (probe < 0 || probe >= cons_probes(ctx, mode)) return fail(ctx, KP_E_INVALID, "probe out of range");
+    const auto t0 = clk::now();
+    kp_ctx* c = ctx;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int P = c->P, NT = c->NT, R = c->R, NC = c->cons.n_cand;
+    c->cx_ms[0] = c->cx_ms[1] = 0;
+    c->cx_counts[0] = c->cx_counts[1] = 0;
+    *needed = 0;
+    // the probe's non-pending pods: its candidates' reschedulable pods
+    const std::vector<int32_t>& coff = c->cons_off;
+    const int cap_pods = std::max(1, mode == KP_CONSOLIDATE_SINGLE ? coff[probe + 1] - coff[probe]
+                                                                     : coff[std::min(NC, probe + 2)] - coff[0]);
+    HIPCHK(c->d_cx_rows.ensure(1));
+    HIPCHK(c->d_cx_pods.ensure(cap_pods));
+    HIPCHK(c->d_cx_rank.ensure(cap_pods));
+    HIPCHK(c->d_cx_cls.ensure(cap_pods));
+    HIPCHK(c->d_cx_shape.ensure(cap_pods));
+    HIPCHK(c->d_cx_rem.ensure(std::max(1, NT * R)));
+    HIPCHK(c->d_cx_nrec.ensure(1));
+    HIPCHK(hipMemsetAsync(c->d_cx_nrec.p, 0, sizeof(int32_t), s));
+    KpConsExplain x{};
+    x.rows = c->d_cx_rows.p;
+    x.pods = c->d_cx_pods.p;
+    x.pod_rank = c->d_cx_rank.p;
+    x.pod_cls = c->d_cx_cls.p;
+    x.pod_shape = c->d_cx_shape.p;
+    x.n_rec = c->d_cx_nrec.p;
+    x.cap_pods = cap_pods;
+    x.rem = c->d_cx_rem.p;
+    float kms = 0;
+    if (const kp_status st = cons_explain_run(ctx, mode, probe, probe + 1, x, &kms); st != KP_OK) return st;
+    kp_probe_explanation row{};
+    HIPCHK(hipMemcpy(&row, c->d_cx_rows.p, sizeof row, hipMemcpyDeviceToHost));
+    c->cx_ms[0] = kms;
+    c->cx_counts[0] = 1;
+    // the pods the queue still held (the pods of a NodeClaim TruncateInstanceTypes dropped were placed by their last
+    // add(): n_unscheduled counts them, they are not listed)
+    int32_t held = 0;
+    HIPCHK(hipMemcpy(&held, c->d_cx_nrec.p, sizeof held, hipMemcpyDeviceToHost));
+    const int n_rec = row.reason == KP_UNCONS_PODS_UNSCHEDULABLE ? std::max(0, std::min(held, cap_pods)) : 0;
+    if (n_rec == 0) {
+        c->cx_ms[1] = ns_since(t0) * 1e-6;
+        return KP_OK;
+    }
+    std::vector<int32_t> pods(n_rec), rank(n_rec), cls(n_rec), shape(n_rec);
+    HIPCHK(hipMemcpy(pods.data(), c->d_cx_pods.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rank.data(), c->d_cx_rank.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cls.data(), c->d_cx_cls.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(shape.data(), c->d_cx_shape.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
+    std::vector<int> ord(n_rec);
+    for (int i = 0; i < n_rec; i++) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](int a, int b) { return rank[a] < rank[b]; });  // queue order
+    const int n_list = max_pods > 0 && max_pods < n_rec ? max_pods : n_rec;
+    *needed = (int64_t)n_list * NT;
+    if (!out || cap < *needed) return fail(ctx, KP_E_BUFFER, "kp_consolidate_explain_pods: " + std::to_string(*needed) + " rows");
+    for (int i = 0; i < n_list; i++)
+        if (pods[ord[i]] < 0 || pods[ord[i]] >= P || cls[ord[i]] < 0 || cls[ord[i]] >= c->C)
+            return fail(ctx, KP_E_DEVICE, "kp_consolidate_explain_pods: inconsistent pod record");
+    // a row is a function of (final shape, template): one representative pod per distinct shape; a class constrained
+    // by a topology group, in a pass that has groups, is not evaluated (the probe's counts are not at hand): of_pod -1
+    std::vector<uint32_t> cflags(std::max(c->C, 1), 0u);
+    if (c->tg_G > 0) HIPCHK(hipMemcpy(cflags.data(), c->d_cls_flags.p, (size_t)c->C * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> rep, rep_cls, of_pod(n_list);
+    {
+        std::unordered_map<int32_t, int32_t> idx;
+        for (int i = 0; i < n_list; i++) {
+            const int q = ord[i];
+            if (c->tg_G > 0 && (cflags[cls[q]] & CF_TOPO_CONS)) {
+                of_pod[i] = -1;
+                continue;
+            }
+            const auto it = idx.emplace(shape[q], (int32_t)rep.size());
+            if (it.second) {
+                rep.push_back(pods[q]);
+                rep_cls.push_back(cls[q]);
+            }
+            of_pod[i] = it.first->second;
+        }
+    }
+    const int S = (int)rep.size();
+    std::vector<KpExplainRow> xrows((size_t)S * NT);
+    if (S > 0) {
+        if ((int)c->h_x_tol.size() < c->C || (int)c->h_x_hblock.size() < c->C)
+            return fail(ctx, KP_E_STATE, "kp_consolidate_explain_pods: the prepared pass kept no toleration table");
+        // explain_kernel reads a representative's class from pod_cls: a per-pod array holding the recorded final classes
+        std::vector<int32_t> pcls(std::max(P, 1), 0);
+        for (int i = 0; i < S; i++) pcls[rep[i]] = rep_cls[i];
+        HIPCHK(c->d_cx_pcls.upload(pcls, s));
+        HIPCHK(c->d_cx_rep.upload(rep, s));
+        HIPCHK(c->d_cx_xrows.ensure((size_t)S * NT));
+        HIPCHK(c->d_cx_tol.upload(c->h_x_tol, s));
+        HIPCHK(c->d_cx_hblock.upload(c->h_x_hblock, s));
+        KpDev d = c->dev;  // a copy: the probe's remaining limits and final classes in place of the pass's
+        d.remaining = c->d_cx_rem.p;
+        d.pod_cls = c->d_cx_pcls.p;
+        d.resv_on = 0;  // the probe's reservation capacities are not at hand: the residual stays KP_WHY_UNKNOWN
+        if (c->tg_G > 0) {
+            d.tg_cnt = c->d_tg_cnt0.p;
+            d.tg_hcnt = c->d_tg_hcnt0.p;
+        }
+        KpExplain ex{};
+        ex.rep = c->d_cx_rep.p;
+        ex.n_shapes = S;
+        ex.born = c->dev.born0;
+        ex.tol = c->d_cx_tol.p;
+        ex.hblock = c->d_cx_hblock.p;
+        ex.rows = c->d_cx_xrows.p;
+        HIPCHK(hipEventRecord(c->cxev[2], s));
+        HIPCHK(kp_launch_explain(d, ex, s));
+        HIPCHK(hipEventRecord(c->cxev[3], s));
+        HIPCHK(hipMemcpyAsync(xrows.data(), c->d_cx_xrows.p, xrows.size() * sizeof(KpExplainRow), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float xms = 0;
+        HIPCHK(hipEventElapsedTime(&xms, c->cxev[2], c->cxev[3]));
+        c->cx_ms[0] += xms;
+    }
+    ExplainKeys keys;
+    bool need_keys = false;
+    for (const KpExplainRow& r : xrows) need_keys |= r.kmask != 0;
+    if (need_keys)
+        if (const kp_status st = keys.load(ctx); st != KP_OK) return st;
+    for (int i = 0; i < n_list; i++)
+        for (int j = 0; j < NT; j++) {
+            static const KpExplainRow none{};  // KPX_UNKNOWN
+            const KpExplainRow& r = of_pod[i] >= 0 ? xrows[(size_t)of_pod[i] * NT + j] : none;
+            kp_pod_explanation& o = out[(size_t)i * NT + j];
+            o.pod = pods[ord[i]];
+            o.nodepool = c->tmpl_np[j];
+            o.reason = r.reason;
+            o.key = (r.kmask || r.hostkey) ? keys.key_of(c, r, rep_cls[of_pod[i]], j) : -1;
+            o.criteria = r.criteria;
+            o.n_options = r.n_options;
+            o.n_requirements = r.n_requirements;
+            o.n_fits = r.n_fits;
+            o.n_offering = r.n_offering;
+        }
+    c->cx_ms[1] = ns_since(t0) * 1e-6;
+    c->cx_counts[1] = (int64_t)S * NT;
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_consolidate_explain_key(kp_ctx* ctx, int32_t key, char* buf, int64_t cap, int64_t* needed) {
+    if (!ctx) return KP_E_INVALID;
+    if (!cons_explainable(ctx)) return fail(ctx, KP_E_STATE, "kp_consolidate_explain_key without a prepared pass");
+    if (key < 0 || key >= ctx->K || key >= (int)ctx->sol.keys.size()) return fail(ctx, KP_E_INVALID, "key index");
+    const std::string& s = ctx->sol.keys[key].name;
+    if (needed) *needed = (int64_t)s.size() + 1;
+    if ((int64_t)s.size() + 1 > cap || !buf) return KP_E_BUFFER;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return KP_OK;
+}
+
+extern "C" kp_status kp_consolidate_explain_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters) {
+    if (!ctx || !ms) return KP_E_INVALID;
+    ms[0] = ctx->cx_ms[0];
+    ms[1] = ctx->cx_ms[1];
+    for (int i = 0; counters && i < n_counters && i < 2; i++) counters[i] = ctx->cx_counts[i];
+    return KP_OK;
 }
 
 extern "C" kp_status kp_consolidate_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters) {

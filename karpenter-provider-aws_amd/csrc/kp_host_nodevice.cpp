@@ -10,4 +10,19 @@ hipError_t kp_launch_explain(const KpDev& d, const KpExplain& x, hipStream_t) {
     for (int i = 0; i < x.n_shapes * d.NT; i++) x.rows[i] = KpExplainRow{};
     return hipSuccess;
 }
+
+// kp_consolidate.hip's explain launcher: the probes run as the stand-in of kp_launch_consolidate runs them, and every row
+// says that the probe has a command (KP_UNCONS_NONE); no pod is recorded.
+hipError_t kp_launch_consolidate_explain(const KpDev& d, const KpCons& k, const KpConsExplain& x, int n_workers,
+                                         hipStream_t s, KpDev* d_dev, KpCons* d_k) {
+    const hipError_t e = kp_launch_consolidate(d, k, n_workers, s, d_dev, d_k);
+    for (int i = 0; i < k.n_probes; i++) {
+        kp_probe_explanation r{};
+        r.first_unscheduled = -1;
+        r.candidate_price = k.out[i].candidate_price;
+        x.rows[i] = r;
+    }
+    if (x.n_rec) x.n_rec[0] = 0;
+    return e;
+}
 #endif

@@ -218,6 +218,28 @@ EXPLANATION_DTYPE = np.dtype([("pod", np.int32), ("nodepool", np.int32), ("reaso
 assert EXPLANATION_DTYPE.itemsize == C.sizeof(kp_pod_explanation)
 
 
+# kp_consolidate_explain: why a probe found no command (kpsim.h KP_UNCONS_*, kp_probe_explanation)
+(KP_UNCONS_NONE, KP_UNCONS_PODS_UNSCHEDULABLE, KP_UNCONS_MULTIPLE_NODECLAIMS, KP_UNCONS_SPOT_TO_SPOT_DISABLED,
+ KP_UNCONS_MIN_VALUES, KP_UNCONS_NOT_CHEAPER, KP_UNCONS_SPOT_TO_SPOT_TOO_FEW, KP_UNCONS_SAME_INSTANCE_TYPE) = range(8)
+UNCONS_NAMES = ["NONE", "PODS_UNSCHEDULABLE", "MULTIPLE_NODECLAIMS", "SPOT_TO_SPOT_DISABLED", "MIN_VALUES", "NOT_CHEAPER",
+                "SPOT_TO_SPOT_TOO_FEW", "SAME_INSTANCE_TYPE"]
+KP_UNCONS_F_UNINITIALIZED_NODE, KP_UNCONS_F_TRUNCATED, KP_UNCONS_F_SPOT_TO_SPOT = 1, 2, 4
+
+
+class kp_probe_explanation(C.Structure):
+    _fields_ = [("reason", C.c_int32), ("flags", C.c_int32), ("n_unscheduled", C.c_int32),
+                ("first_unscheduled", C.c_int32), ("n_options", C.c_int32), ("n_cheaper", C.c_int32),
+                ("min_needed", C.c_int32), ("pad", C.c_int32), ("candidate_price", C.c_double),
+                ("cheapest_price", C.c_double)]
+
+
+PROBE_EXPLANATION_DTYPE = np.dtype([("reason", np.int32), ("flags", np.int32), ("n_unscheduled", np.int32),
+                                    ("first_unscheduled", np.int32), ("n_options", np.int32), ("n_cheaper", np.int32),
+                                    ("min_needed", np.int32), ("pad", np.int32), ("candidate_price", np.float64),
+                                    ("cheapest_price", np.float64)])
+assert PROBE_EXPLANATION_DTYPE.itemsize == C.sizeof(kp_probe_explanation)
+
+
 KP_FILTER_NAMES = ["compatible-available-filter", "capacity-reservation-type-filter", "capacity-block-filter",
                    "reserved-offering-filter", "exotic-instance-filter", "spot-instance-filter"]  # filter.go Name()
 KP_N_FILTERS = 6

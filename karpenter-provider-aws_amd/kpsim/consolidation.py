@@ -201,12 +201,25 @@ class Consolidator:
     def replacement(self, cp: model.ConsolidationProblem, mode, probe) -> Command:
         """kp_consolidate_replacement of one probe; prepares the pass first unless the ctx still holds this process's
         pass of (cp, mode): nothing else (a Solve, another pass, a catalog change) ran on the ctx since (pass_gen)."""
+        self._ensure_prepared(cp, mode)
+        return self.ctx.consolidate_replacement(mode, probe)
+
+    def _ensure_prepared(self, cp, mode, any_mode=False):
+        """Prepares the pass of cp unless the ctx still holds this process's pass of (cp, mode), or, with any_mode, of cp
+        (a prepared pass serves both modes)."""
         prep = getattr(self, "_prepared", None)
-        if prep is None or prep[0] is not cp or prep[1] != mode or prep[2] != self.ctx.pass_gen:
+        if prep is None or prep[0] is not cp or (prep[1] != mode and not any_mode) or prep[2] != self.ctx.pass_gen:
             v = model.ConsolidateInputView(cp, mode, 0, 0, self.spot_to_spot, self.max_candidates)
             self.ctx.consolidate_prepare(v)
             self._prepared = (cp, mode, self.ctx.pass_gen, v)
-        return self.ctx.consolidate_replacement(mode, probe)
+
+    def explain(self, cp: model.ConsolidationProblem, mode) -> np.ndarray:
+        """kp_consolidate_explain of every probe of `mode` (SINGLE or MULTI): why it found no command, one row of
+        abi.PROBE_EXPLANATION_DTYPE per probe, like probes().  Prepares the pass first unless the ctx still holds this
+        process's pass of cp (the prepared pass serves either mode)."""
+        self._ensure_prepared(cp, mode, any_mode=True)
+        n = model.consolidation_probe_count(len(cp.candidates), mode, self.max_candidates)
+        return self.ctx.consolidate_explain(mode, n)
 
     def compute_command(self, cp: model.ConsolidationProblem, mode, group=None) -> Command:
         """The Command of one method, with the replacement NodeClaim of a REPLACE (kp_consolidate_replacement over this

@@ -14,7 +14,8 @@ EXPORTS = [
     "kp_consolidate_stats", "kp_consolidate_prepare", "kp_consolidate_execute", "kp_launch_select", "kp_launch_stats",
     "kp_nodeclaim_labels", "kp_catalog_build", "kp_catalog_get_view", "kp_catalog_overhead", "kp_catalog_resource_name",
     "kp_catalog_free", "kp_consolidate_command", "kp_consolidate_replacement", "kp_solve_volume_encoding",
-    "kp_solve_explain", "kp_solve_explain_key", "kp_solve_explain_stats",
+    "kp_solve_explain", "kp_solve_explain_key", "kp_solve_explain_stats", "kp_consolidate_explain",
+    "kp_consolidate_explain_pods", "kp_consolidate_explain_key", "kp_consolidate_explain_stats",
 ]
 
 _lib = None
@@ -67,6 +68,13 @@ def load():
     L.kp_consolidate_command.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.kp_consolidation_command)]
     if hasattr(L, "kp_consolidate_replacement"):  # (absent from pre-round-5 libraries, A/B only)
         L.kp_consolidate_replacement.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.kp_consolidation_command)]
+    if hasattr(L, "kp_consolidate_explain"):  # (absent from older libraries, A/B only)
+        L.kp_consolidate_explain.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.POINTER(abi.kp_probe_explanation), C.c_int32]
+        L.kp_consolidate_explain_pods.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.POINTER(abi.kp_pod_explanation), C.c_int64, C.POINTER(C.c_int64)]
+        L.kp_consolidate_explain_key.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.kp_consolidate_explain_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
     L.kp_launch_select.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.kp_launch_request), C.c_int32,
                                    C.POINTER(abi.kp_launch_result), C.POINTER(C.c_int32), C.c_int32,
                                    C.POINTER(C.c_int32), C.c_int32]
@@ -304,6 +312,51 @@ class Context:
         ms = (C.c_double * 3)()
         ct = (C.c_int64 * 20)()
         self.check(self.L.kp_consolidate_stats(self.h, ms, ct, 20), "kp_consolidate_stats")
+        return list(ms), list(ct)
+
+    def consolidate_explain(self, mode, n_probes, begin=0, end=0):
+        """kp_consolidate_explain: why each probe [begin, end) of `mode` (SINGLE or MULTI) of the prepared pass found no
+        command -> numpy array of abi.PROBE_EXPLANATION_DTYPE; n_probes = the mode's probe count."""
+        import numpy as np
+        b1 = end if 0 < end < n_probes else n_probes
+        out = np.zeros(max(1, b1 - begin), abi.PROBE_EXPLANATION_DTYPE)
+        self.check(self.L.kp_consolidate_explain(self.h, mode, begin, end,
+                                                 out.ctypes.data_as(C.POINTER(abi.kp_probe_explanation)), len(out)),
+                   "kp_consolidate_explain")
+        return out[:max(0, b1 - begin)]
+
+    def consolidate_explain_pods(self, mode, probe, max_pods=0):
+        """kp_consolidate_explain_pods: the first max_pods (<= 0: all) non-pending pods a PODS_UNSCHEDULABLE probe left
+        without a place, one row per (pod, NodePool) as abi.EXPLANATION_DTYPE; empty for any other probe."""
+        import numpy as np
+        need = C.c_int64(0)
+        st = self.L.kp_consolidate_explain_pods(self.h, mode, probe, max_pods, None, 0, C.byref(need))
+        if st not in (abi.KP_OK, abi.KP_E_BUFFER):
+            self.check(st, "kp_consolidate_explain_pods")
+        out = np.zeros(max(1, need.value), abi.EXPLANATION_DTYPE)
+        if need.value:
+            self.check(self.L.kp_consolidate_explain_pods(self.h, mode, probe, max_pods,
+                                                          out.ctypes.data_as(C.POINTER(abi.kp_pod_explanation)), len(out),
+                                                          C.byref(need)), "kp_consolidate_explain_pods")
+        return out[:need.value]
+
+    def consolidate_explain_key(self, key):
+        """Name of key `key` of a kp_consolidate_explain_pods row (kp_consolidate_explain_key)."""
+        need = C.c_int64(0)
+        buf = C.create_string_buffer(256)
+        st = self.L.kp_consolidate_explain_key(self.h, key, buf, len(buf), C.byref(need))
+        if st == abi.KP_E_BUFFER:
+            buf = C.create_string_buffer(need.value)
+            st = self.L.kp_consolidate_explain_key(self.h, key, buf, len(buf), C.byref(need))
+        self.check(st, "kp_consolidate_explain_key")
+        return buf.value.decode()
+
+    def consolidate_explain_stats(self):
+        """(ms[kernels, whole call], counters[probes explained, (shape, NodePool) pairs diagnosed]) of the last
+        consolidate_explain() / consolidate_explain_pods()."""
+        ms = (C.c_double * 2)()
+        ct = (C.c_int64 * 2)()
+        self.check(self.L.kp_consolidate_explain_stats(self.h, ms, ct, 2), "kp_consolidate_explain_stats")
         return list(ms), list(ct)
 
     def close(self):
