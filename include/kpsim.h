@@ -926,6 +926,126 @@ kp_status kp_consolidate_explain_key(kp_ctx* ctx, int32_t key, char* buf, int64_
  * the whole call; counters[0] probes explained, [1] (shape, NodePool) pairs diagnosed.  n_counters up to 2. */
 kp_status kp_consolidate_explain_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters);
 
+/*
+ * SimulateScheduling results — the raw scheduling.Results of a probe of a prepared pass, for the two consumers of
+ * [core] disruption's SimulateScheduling (helpers.go, recalled) that computeConsolidation does not serve:
+ *   Drift (website/content/en/preview/concepts/disruption.md:132-165; [core] disruption/drift.go, recalled) replaces a
+ *     drifted node by whatever the simulation produces, any number of NodeClaims;
+ *   command validation ([core] disruption/validation.go ValidateCommand, recalled) re-simulates a consolidation command
+ *     after its TTL and accepts a REPLACE only if the command's instance types are a subset of the re-simulated
+ *     NodeClaim's InstanceTypeOptions — the list before computeConsolidation's price filter, which
+ *     kp_consolidate_replacement does not return.
+ * The consolidation probes stop at their second new NodeClaim (kp_probe_result.n_new_nodeclaims caps at 2, and still
+ * does).  These calls run the same probes — the same lists, kp_consolidate_execute's numbering — on a separate kernel
+ * (kp_simulate.hip) to the end of their queue, with up to KP_SIM_MAX_NODECLAIMS new NodeClaims, and return
+ * Solve(...).TruncateInstanceTypes(max_instance_types): every new NodeClaim with its truncated, price-ordered options,
+ * requirements and NodePool, where each pod went, and AllNonPendingPodsScheduled.
+ *
+ * All need a prepared pass (kp_consolidate_prepare; KP_E_STATE otherwise, as for kp_consolidate_explain), run on the
+ * primary device of a multi-device ctx, and write nothing the pass keeps: kp_consolidate_execute, _command and _stats
+ * return what they would have returned.
+ *
+ * Refused, never approximated.  Pass-wide, KP_E_UNSUPPORTED with a message: a cluster with topology terms; a catalog
+ * with reserved offerings (the kernel runs the evaluation without reserved-offering rows; with the ReservedCapacity
+ * gate on, the oracle's only entry point that runs the fallback reservation mode does not return NodeClaims past the
+ * second, so nothing could check it); pod classes with preferences that can relax.  Per probe, KP_SIM_UNSUPPORTED_PROBE:
+ * a probe that reschedules a host-port pod or a pod with claims on a limited CSI driver (the per-probe port and claim
+ * overlays of the consolidation pass are not modelled; a probe that reschedules a mutator's pod is covered: it applies
+ * ExistingNode.Add's requirement merge to its own copies of the nodes it changes, as the pass does).  A probe whose
+ * simulation needs a 13th NodeClaim is KP_SIM_NODECLAIM_OVERFLOW (Go sorts the NodeClaim slice with insertionSort only up
+ * to 12 elements).
+ */
+enum { KP_SIM_MAX_NODECLAIMS = 12 };
+enum { KP_SIM_OK = 0, KP_SIM_NODECLAIM_OVERFLOW = 1, KP_SIM_UNSUPPORTED_PROBE = 2 };
+typedef struct kp_sim_result {
+    int32_t status;            /* KP_SIM_*; every other field is 0 unless KP_SIM_OK */
+    int32_t all_scheduled;     /* Results.AllNonPendingPodsScheduled, after truncation */
+    int32_t n_new_nodeclaims;  /* valid NodeClaims after TruncateInstanceTypes, 0..12 */
+    int32_t n_dropped;         /* NodeClaims the truncation's minValues check dropped */
+    int32_t n_pods;            /* pods the probe rescheduled (pending included) */
+    int32_t n_unscheduled;     /* non-pending pods without a place (those of a dropped NodeClaim included) */
+} kp_sim_result;
+/* rows[i] is probe probe_begin + i of `mode` (KP_CONSOLIDATE_SINGLE or _MULTI; probe_end <= 0: to the end).
+ * KP_E_BUFFER when cap_rows is smaller than the range (nothing is launched). */
+kp_status kp_simulate_execute(kp_ctx* ctx, int32_t mode, int32_t probe_begin, int32_t probe_end,
+                              kp_sim_result* rows, int32_t cap_rows);
+
+/* The Results of one probe, in the shape of kp_solve_output.  NodeClaims are numbered in creation order and include
+ * the ones TruncateInstanceTypes dropped (nodepool -1, their pods KP_POD_UNSCHEDULABLE), as kp_solve_fetch reports
+ * them.  pods[] lists the probe's pods — the pending pods in the input's order, then each candidate's reschedulable
+ * pods in candidate order — as indices into cluster.pods; pod_result[i] / pod_order[i] belong to pods[i], an existing
+ * node being KP_POD_EXISTING(j) with j the index into cluster.existing.  A row that is not KP_SIM_OK returns no
+ * NodeClaims and no pods.  KP_E_BUFFER (with n_type_ids / n_pods set) when a buffer is too small. */
+typedef struct kp_sim_nodeclaims {
+    /* caller-set buffers */
+    int32_t cap_type_ids;
+    int32_t* type_ids;                /* [cap_type_ids] truncated, price-ordered catalog rows */
+    int32_t cap_pods;
+    int32_t* pods;                    /* [cap_pods] */
+    int32_t* pod_result;              /* [cap_pods] */
+    int32_t* pod_order;               /* [cap_pods] position of the pod's placement among the probe's placements, -1 */
+    /* results */
+    kp_sim_result row;
+    int32_t n_nodeclaims;             /* NodeClaims created, dropped ones included */
+    int32_t n_type_ids;
+    int32_t n_pods;
+    int32_t nodeclaim_nodepool[KP_SIM_MAX_NODECLAIMS];      /* index into cluster.nodepools, -1: dropped */
+    int32_t nodeclaim_n_pods[KP_SIM_MAX_NODECLAIMS];
+    int32_t nodeclaim_slice_pos[KP_SIM_MAX_NODECLAIMS];     /* position in s.newNodeClaims at the end of Solve */
+    int32_t nodeclaim_n_options[KP_SIM_MAX_NODECLAIMS];     /* InstanceTypeOptions before truncation */
+    int32_t nodeclaim_type_offset[KP_SIM_MAX_NODECLAIMS + 1];
+} kp_sim_nodeclaims;
+kp_status kp_simulate_nodeclaims(kp_ctx* ctx, int32_t mode, int32_t probe, kp_sim_nodeclaims* out);
+/* Requirements of NodeClaim `nc` of the last kp_simulate_nodeclaims, in kp_result_nodeclaim_requirements' text format
+ * (valid until the ctx's next prepare, catalog upload or availability patch). */
+kp_status kp_simulate_nodeclaim_requirements(kp_ctx* ctx, int32_t nc, char* buf, int64_t cap, int64_t* needed);
+
+/*
+ * Drift's command over the prepared candidates, in their given order — the caller passes them in drifted-time order,
+ * already filtered by NodePool disruption budgets, as for consolidation.  Restated from [core] disruption/drift.go
+ * ComputeCommand (recalled; the module is not vendored):
+ *   - if any candidate has no reschedulable pods, the command is all of those and nothing is simulated;
+ *   - otherwise it is the first candidate whose SimulateScheduling schedules every non-pending pod (candidates that do
+ *     not are skipped: core publishes a Blocked event for them), with results.NewNodeClaims as its replacements — any
+ *     number of them; read them with kp_simulate_nodeclaims(ctx, KP_CONSOLIDATE_SINGLE, candidate, ...);
+ *   - otherwise there is no command.
+ * A candidate whose row is not KP_SIM_OK, met before a decision, ends the call with KP_E_UNSUPPORTED and
+ * failed_candidate set.
+ */
+enum { KP_DRIFT_NONE = 0, KP_DRIFT_DELETE_EMPTY = 1, KP_DRIFT_REPLACE = 2 };
+typedef struct kp_drift_command_out {
+    /* caller-set buffer */
+    int32_t cap_candidates;
+    int32_t* candidates;       /* [cap_candidates] the command's candidates (indices into the prepared candidates) */
+    /* results */
+    int32_t decision;          /* KP_DRIFT_* */
+    int32_t n_candidates;      /* DELETE_EMPTY: the empty candidates; REPLACE: 1; NONE: 0 */
+    int32_t n_nodeclaims;      /* REPLACE: the replacements (0: the node's pods fit the rest of the cluster) */
+    int32_t failed_candidate;  /* KP_E_UNSUPPORTED: the candidate whose row is not KP_SIM_OK, else -1 */
+    kp_sim_result row;         /* REPLACE: the chosen candidate's row */
+} kp_drift_command_out;  /* (a C typedef cannot share the function's name) */
+kp_status kp_drift_command(kp_ctx* ctx, kp_drift_command_out* out);
+
+/*
+ * The tail of [core] disruption/validation.go ValidateCommand (recalled) for the command of probe `probe` of `mode`,
+ * computed on the host from the probe's simulation over the prepared pass (prepare the cluster as it is at validation
+ * time): had_replacement / type_ids are the command's (kp_consolidation_command.decision == REPLACE and its type_ids).
+ * A probe whose row is not KP_SIM_OK: KP_E_UNSUPPORTED.
+ */
+enum { KP_VALIDATE_VALID = 0,
+       KP_VALIDATE_PODS_UNSCHEDULABLE = 1,    /* !Results.AllNonPendingPodsScheduled() */
+       KP_VALIDATE_NO_NODECLAIM = 2,          /* the simulation needs no NodeClaim, the command has a replacement */
+       KP_VALIDATE_MULTIPLE_NODECLAIMS = 3,   /* the simulation needs more than one */
+       KP_VALIDATE_NEEDS_NODECLAIM = 4,       /* the simulation needs one, the command has none (a DELETE) */
+       KP_VALIDATE_NOT_SUBSET = 5 };          /* the command's types are not all among the NodeClaim's truncated options */
+kp_status kp_consolidate_validate(kp_ctx* ctx, int32_t mode, int32_t probe, int32_t had_replacement, int32_t n_type_ids,
+                                  const int32_t* type_ids, int32_t* verdict);
+
+/* The last simulate / drift / validate call: ms[3] = {simulate_kernel, finalize_kernel (HIP events, summed over the
+ * call's batches), whole call}; counters[6] = {pods popped, NodeClaim evaluations, template evaluations, probes run,
+ * KP_SIM_NODECLAIM_OVERFLOW rows, KP_SIM_UNSUPPORTED_PROBE rows}.  n_counters up to 6. */
+kp_status kp_simulate_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters);
+
 #ifdef __cplusplus
 }
 #endif

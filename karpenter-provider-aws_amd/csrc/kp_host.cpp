@@ -631,6 +631,25 @@ struct kp_ctx {
     hipEvent_t cxev[4] = {};
     double cx_ms[2] = {};
     int64_t cx_counts[2] = {};
+    // kp_simulate_*: valid as long as kp_consolidate_explain is (cx_ok); slabs and scratch of its own — the NodeClaim slabs
+    // in the Solve's nc_* layout ([KP_SIM_MAX_NODECLAIMS][workers]), the workers' rings, delta slabs and queue bitmaps —
+    // so nothing the pass or a Solve keeps is touched; events, the last call's figures, and the last
+    // kp_simulate_nodeclaims' requirement digests (kp_simulate_nodeclaim_requirements)
+    DBuf<ReqHdr> d_sm_hdr, d_sm_ov_hdr;
+    DBuf<uint64_t> d_sm_words, d_sm_opts, d_sm_pbits, d_sm_ov_words;
+    DBuf<int64_t> d_sm_req, d_sm_delta, d_sm_stats;
+    DBuf<int32_t> d_sm_tmpl, d_sm_count, d_sm_npods, d_sm_spos, d_sm_nopts, d_sm_valid, d_sm_types, d_sm_ntypes,
+        d_sm_nonpend, d_sm_log, d_sm_nlog, d_sm_err, d_sm_ring, d_sm_rlast, d_sm_ov_slot;
+    DBuf<KpSimRow> d_sm_rows;
+    DBuf<KpDev> d_sm_dev;
+    DBuf<KpCons> d_sm_k;
+    DBuf<KpSim> d_sm_x;
+    hipEvent_t smev[3] = {};
+    double sm_ms[3] = {};
+    int64_t sm_counts[6] = {};
+    int sm_last_n = 0;                       // NodeClaims of the last kp_simulate_nodeclaims
+    std::vector<ReqHdr> sm_last_h;           // [sm_last_n][K]
+    std::vector<uint64_t> sm_last_w;         // [sm_last_n][DW]
 };
 
 static kp_status fail(kp_ctx* c, kp_status st, const std::string& msg) {
@@ -741,6 +760,8 @@ extern "C" kp_status kp_ctx_destroy(kp_ctx* ctx) {
     for (auto& e : ctx->xev)
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->cxev)
+        if (e) hipEventDestroy(e);
+    for (auto& e : ctx->smev)
         if (e) hipEventDestroy(e);
     if (ctx->lstream2) {
         hipStreamSynchronize(ctx->lstream2);
@@ -5176,6 +5197,492 @@ extern "C" kp_status kp_consolidate_stats(kp_ctx* ctx, double* ms, int64_t* coun
     if (counters)
         for (int i = 0; i < n_counters && i < CS_COUNT + 2; i++)
             counters[i] = i < CS_COUNT ? ctx->cons_stats[i] : i == CS_COUNT ? ctx->n_pass_launches : ctx->n_readbacks;
+    return KP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SimulateScheduling results (kp_simulate.hip): the probes of a prepared pass run to the end of their queue with up to
+// KP_SIM_MAX_NODECLAIMS new NodeClaims, then finalize_kernel over their slabs; drift's and ValidateCommand's loops over
+// the rows on the host
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct SimDetail {  // one probe's Results as the device left them
+    int n_nc = 0, n_log = 0;
+    std::vector<int32_t> npods, spos, nopts, valid, ntypes, tmpl, types, log;
+    std::vector<ReqHdr> h;
+    std::vector<uint64_t> w;
+};
+}  // namespace
+
+// The checks every simulate entry point starts with: a prepared pass, a mode with a probe list, and the pass-wide
+// refusals of this first cut (include/kpsim.h).
+static kp_status sim_check(kp_ctx* ctx, const char* who, int mode) {
+    if (mode != KP_CONSOLIDATE_SINGLE && mode != KP_CONSOLIDATE_MULTI)
+        return fail(ctx, KP_E_INVALID, std::string(who) + ": mode must be SINGLE or MULTI");
+    if (!cons_explainable(ctx))
+        return fail(ctx, KP_E_STATE, std::string(who) + " needs a prepared pass (none since the last prepare, catalog "
+                                                        "upload or availability patch)");
+    if (ctx->cons.G > 0)
+        return fail(ctx, KP_E_UNSUPPORTED, std::string(who) + ": the cluster has topology terms (the simulate kernel keeps no "
+                                                              "per-probe topology counts)");
+    if (ctx->dev.ro)
+        return fail(ctx, KP_E_UNSUPPORTED, std::string(who) + ": the catalog has reserved offerings (the simulate kernel "
+                                                              "evaluates NodeClaims without reserved-offering rows)");
+    if (ctx->dev.relax_next)
+        return fail(ctx, KP_E_UNSUPPORTED, std::string(who) + ": a pod class has preferences that can relax (the simulate "
+                                                              "kernel's queue holds no relaxed entries)");
+    return KP_OK;
+}
+
+static void sim_begin(kp_ctx* c) {
+    c->sm_ms[0] = c->sm_ms[1] = c->sm_ms[2] = 0;
+    for (int64_t& v : c->sm_counts) v = 0;
+}
+
+// Probes [b0, b1) of `mode` in batches of one worker per probe (a batch's slabs must survive until its finalize), rows
+// into rows[b1 - b0]; det (one probe only): its NodeClaims, placements and requirement digests.  Timings and counters
+// accumulate into ctx->sm_ms / sm_counts.
+static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* rows, SimDetail* det) try {
+    kp_ctx* c = ctx;
+    const int n = b1 - b0;
+    if (n <= 0) return KP_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (!c->cons_prep_valid) {
+        // the device prep of the prepared cluster (queue order, class / template / existing-node masks) is computed by
+        // whichever call runs first after the prepare: here by one probe of the pass, whose figures are not kept
+        double ms_keep[3];
+        int64_t st_keep[CS_COUNT];
+        memcpy(ms_keep, c->cons_ms, sizeof ms_keep);
+        memcpy(st_keep, c->cons_stats, sizeof st_keep);
+        kp_probe_result row{};
+        const kp_status st = cons_run(ctx, 0, 0, 0, 1, nullptr, &row);
+        memcpy(c->cons_ms, ms_keep, sizeof ms_keep);
+        memcpy(c->cons_stats, st_keep, sizeof st_keep);
+        if (st != KP_OK) return st;
+        if (!c->cons_prep_valid) return fail(ctx, KP_E_STATE, "simulate: the prepared pass has no device prep");
+    }
+    for (auto& e : c->smev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    KpDev d = c->dev;
+    const size_t E = std::max(d.E, 1), A = std::max(d.n_active, 1), K = std::max(d.K, 1), DW = std::max(d.DW, 1),
+                 TW = std::max(d.TW, 1), R = std::max(d.R, 1), M = std::max(d.M, 1);
+    const size_t NCM = KP_SIM_MAX_NODECLAIMS;
+    d.lds_A = 0;  // no quick-accept witness in probes
+    d.lds_nstage = d.n_active;
+    d.profile = 0;
+    d.queue0 = c->cons_q0;
+    d.resv_on = 0;
+    d.nc_held = nullptr;
+    KpCons k = c->cons;
+    const int NC = k.n_cand;
+    const std::vector<int32_t>& coff = c->cons_off;
+    if ((int)coff.size() < NC + 1) return fail(ctx, KP_E_STATE, "simulate: the prepared pass kept no candidate offsets");
+    int maxp = 0;  // ring capacity: pods of the largest probe
+    if (mode == KP_CONSOLIDATE_SINGLE)
+        for (int i = b0; i < b1; i++) maxp = std::max(maxp, coff[i + 1] - coff[i]);
+    else
+        maxp = coff[std::min(NC, b1 + 1)] - coff[0];
+    k.mode = mode;
+    k.ring_cap = std::max(1, c->cons_n_pending + maxp);
+    KpSim x{};
+    if (!kp_sim_plan_lds(d, x, KP_LDS_BYTES)) return fail(ctx, KP_E_UNSUPPORTED, "simulate LDS plan exceeds 160 KB");
+    // batch size: the workers' slabs and scratch stay within about 64 MB
+    // a MUT probe copies a node's digest when a merge first changes it: at most once per node and per pod it places
+    x.ov_cap = k.mut ? (int)std::max<size_t>(1, std::min<size_t>(E, (size_t)k.ring_cap)) : 1;
+    const size_t per = NCM * (K * sizeof(ReqHdr) + DW * 8 + TW * 8 + R * 8 + M * 4 + 40) + (size_t)k.ring_cap * 16 +
+                       A * E * 8 + (size_t)k.PW * 8 +
+                       (k.mut ? E * 4 + (size_t)x.ov_cap * (K * sizeof(ReqHdr) + DW * 8) : 0);
+    const int W = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)64 << 20) / per)));
+    const size_t WN = (size_t)W * NCM;
+    if (c->d_sm_hdr.n < WN * K) {
+        HIPCHK(c->d_sm_hdr.ensure(WN * K));
+        HIPCHK(hipMemsetAsync(c->d_sm_hdr.p, 0, WN * K * sizeof(ReqHdr), s));
+    }
+    if (c->d_sm_words.n < WN * DW) {
+        HIPCHK(c->d_sm_words.ensure(WN * DW));
+        HIPCHK(hipMemsetAsync(c->d_sm_words.p, 0, WN * DW * 8, s));
+    }
+    const size_t pb = (size_t)W * k.PW;
+    if (c->d_sm_pbits.n < pb) {  // kept all-zero between probes by the kernel
+        HIPCHK(c->d_sm_pbits.ensure(pb));
+        HIPCHK(hipMemsetAsync(c->d_sm_pbits.p, 0, pb * 8, s));
+    }
+    HIPCHK(c->d_sm_opts.ensure(WN * TW));
+    HIPCHK(c->d_sm_req.ensure(WN * R));
+    HIPCHK(c->d_sm_tmpl.ensure(WN));
+    HIPCHK(c->d_sm_count.ensure(1));
+    HIPCHK(c->d_sm_npods.ensure(WN));
+    HIPCHK(c->d_sm_spos.ensure(WN));
+    HIPCHK(c->d_sm_nopts.ensure(WN));
+    HIPCHK(c->d_sm_valid.ensure(WN));
+    HIPCHK(c->d_sm_types.ensure(WN * M));
+    HIPCHK(c->d_sm_ntypes.ensure(WN));
+    HIPCHK(c->d_sm_nonpend.ensure(WN));
+    HIPCHK(c->d_sm_log.ensure((size_t)W * k.ring_cap * 2));
+    HIPCHK(c->d_sm_nlog.ensure(W));
+    HIPCHK(c->d_sm_err.ensure(1));
+    HIPCHK(c->d_sm_stats.ensure(SS_COUNT));
+    HIPCHK(c->d_sm_ring.ensure((size_t)W * k.ring_cap));
+    HIPCHK(c->d_sm_rlast.ensure((size_t)W * k.ring_cap));
+    HIPCHK(c->d_sm_delta.ensure((size_t)W * A * E));
+    HIPCHK(c->d_sm_rows.ensure(W));
+    HIPCHK(c->d_sm_ov_slot.ensure(k.mut ? (size_t)W * E : 1));
+    HIPCHK(c->d_sm_ov_hdr.ensure((size_t)W * x.ov_cap * K));
+    HIPCHK(c->d_sm_ov_words.ensure((size_t)W * x.ov_cap * DW));
+    HIPCHK(c->d_sm_dev.ensure(1));
+    HIPCHK(c->d_sm_k.ensure(1));
+    HIPCHK(c->d_sm_x.ensure(1));
+    HIPCHK(hipMemsetAsync(c->d_sm_err.p, 0, sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(c->d_sm_stats.p, 0, SS_COUNT * sizeof(int64_t), s));
+    // the NodeClaim slabs in place of the Solve's state and outputs (finalize_kernel reads and writes them through d)
+    d.nc_hdr = c->d_sm_hdr.p;
+    d.nc_words = c->d_sm_words.p;
+    d.nc_opts = c->d_sm_opts.p;
+    d.nc_req = c->d_sm_req.p;
+    d.nc_tmpl = c->d_sm_tmpl.p;
+    d.nc_count = c->d_sm_count.p;
+    d.nc_npods = c->d_sm_npods.p;
+    d.nc_slice_pos = c->d_sm_spos.p;
+    d.nc_nopts = c->d_sm_nopts.p;
+    d.nc_valid = c->d_sm_valid.p;
+    d.nc_types = c->d_sm_types.p;
+    d.nc_ntypes = c->d_sm_ntypes.p;
+    k.cand_i = c->d_cand_i.p;
+    k.cand_off = c->d_cand_off.p;
+    k.cand_pods = c->d_cand_pods.p;
+    k.cand_price = c->d_cand_price.p;
+    k.cand_cap = c->d_cand_cap.p;
+    k.rank = c->d_rank.p;
+    k.pend_bits = c->d_pend_bits.p;
+    k.init_bits = c->d_init.p;
+    k.n_pending = c->cons_n_pending;
+    k.alloc_act = c->d_alloc_act.p;
+    k.mut_s = c->d_mut_s.p;
+    k.mut_m = c->d_mut_m.p;
+    k.ring = c->d_sm_ring.p;
+    k.ring_last = c->d_sm_rlast.p;
+    k.delta = c->d_sm_delta.p;
+    k.pbits = c->d_sm_pbits.p;
+    k.relax = 0;
+    x.rows = c->d_sm_rows.p;
+    x.nc_nonpend = c->d_sm_nonpend.p;
+    x.log = c->d_sm_log.p;
+    x.n_log = c->d_sm_nlog.p;
+    x.stats = c->d_sm_stats.p;
+    x.err = c->d_sm_err.p;
+    x.ov_slot = c->d_sm_ov_slot.p;
+    x.ov_hdr = c->d_sm_ov_hdr.p;
+    x.ov_words = c->d_sm_ov_words.p;
+    std::vector<KpSimRow> dr(W);
+    std::vector<int32_t> valid(WN), nonpend(WN);
+    for (int q0 = b0; q0 < b1; q0 += W) {
+        const int nb = std::min(W, b1 - q0);
+        const int32_t count = nb * (int)NCM;
+        k.n_probes = nb;
+        k.probe0 = q0;
+        d.NCcap = count;
+        HIPCHK(hipMemcpyAsync(c->d_sm_count.p, &count, sizeof count, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_sm_dev.p, &d, sizeof(KpDev), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_sm_k.p, &k, sizeof(KpCons), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_sm_x.p, &x, sizeof(KpSim), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(c->smev[0], s));
+        HIPCHK(kp_launch_simulate(k, x, s, c->d_sm_dev.p, c->d_sm_k.p, c->d_sm_x.p));
+        HIPCHK(hipEventRecord(c->smev[1], s));
+        int32_t err = 0;
+        HIPCHK(hipMemcpyAsync(dr.data(), c->d_sm_rows.p, (size_t)nb * sizeof(KpSimRow), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&err, c->d_sm_err.p, sizeof err, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c->smev[0], c->smev[1]));
+        c->sm_ms[0] += ms;
+        if (err) return fail(ctx, KP_E_DEVICE, "simulate_kernel: a probe exceeded its pop bound (internal error)");
+        // the slabs are NodeClaim-major over the batch: finalize_kernel runs over the entries of the NodeClaims the batch
+        // created (most NodeClaims of any probe x workers) and leaves the rest alone
+        int most = 0;
+        for (int i = 0; i < nb; i++) {
+            if (dr[i].status == KP_SIM_OK && (dr[i].n_nc < 0 || dr[i].n_nc > (int)NCM))
+                return fail(ctx, KP_E_DEVICE, "simulate_kernel: inconsistent row");
+            if (dr[i].status == KP_SIM_OK) most = std::max(most, dr[i].n_nc);
+        }
+        const int32_t used = most * nb;
+        if (used > 0) {
+            HIPCHK(hipMemcpyAsync(c->d_sm_count.p, &used, sizeof used, hipMemcpyHostToDevice, s));
+            HIPCHK(hipEventRecord(c->smev[1], s));
+            HIPCHK(kp_launch_finalize(d, used, s));
+            HIPCHK(hipEventRecord(c->smev[2], s));
+            HIPCHK(hipMemcpyAsync(valid.data(), c->d_sm_valid.p, (size_t)used * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(nonpend.data(), c->d_sm_nonpend.p, (size_t)used * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipEventElapsedTime(&ms, c->smev[1], c->smev[2]));
+            c->sm_ms[1] += ms;
+        }
+        for (int i = 0; i < nb; i++) {
+            const KpSimRow& r = dr[i];
+            kp_sim_result o{};
+            o.status = r.status;
+            if (r.status == KP_SIM_OK) {
+                int dropped = 0, lost = 0;
+                for (int q = 0; q < r.n_nc; q++)
+                    if (!valid[(size_t)q * nb + i]) {  // TruncateInstanceTypes dropped it: its pods get errors
+                        dropped++;
+                        lost += nonpend[(size_t)q * nb + i];
+                    }
+                const int ok = r.ok_np - lost;
+                o.all_scheduled = (!r.bad && ok == r.n_np) ? 1 : 0;
+                o.n_new_nodeclaims = r.n_nc - dropped;
+                o.n_dropped = dropped;
+                o.n_pods = r.n_pods;
+                o.n_unscheduled = r.n_np - ok;
+            } else if (r.status == KP_SIM_NODECLAIM_OVERFLOW) {
+                c->sm_counts[4]++;
+            } else {
+                c->sm_counts[5]++;
+            }
+            rows[q0 - b0 + i] = o;
+        }
+        if (det && nb == 1 && dr[0].status == KP_SIM_OK) {
+            SimDetail& t = *det;
+            const int N = dr[0].n_nc;
+            t.n_nc = N;
+            t.npods.resize(N), t.spos.resize(N), t.nopts.resize(N), t.valid.resize(N), t.ntypes.resize(N), t.tmpl.resize(N);
+            t.types.resize((size_t)N * M), t.h.resize((size_t)N * K), t.w.resize((size_t)N * DW);
+            HIPCHK(hipMemcpy(&t.n_log, c->d_sm_nlog.p, 4, hipMemcpyDeviceToHost));
+            if (t.n_log < 0 || t.n_log > k.ring_cap) return fail(ctx, KP_E_DEVICE, "simulate_kernel: inconsistent placement log");
+            t.log.resize((size_t)t.n_log * 2);
+            if (t.n_log) HIPCHK(hipMemcpy(t.log.data(), c->d_sm_log.p, (size_t)t.n_log * 8, hipMemcpyDeviceToHost));
+            if (N > 0) {
+                HIPCHK(hipMemcpy(t.npods.data(), c->d_sm_npods.p, N * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.spos.data(), c->d_sm_spos.p, N * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.nopts.data(), c->d_sm_nopts.p, N * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.valid.data(), c->d_sm_valid.p, N * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.ntypes.data(), c->d_sm_ntypes.p, N * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.tmpl.data(), c->d_sm_tmpl.p, N * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.types.data(), c->d_sm_types.p, (size_t)N * M * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.h.data(), c->d_sm_hdr.p, (size_t)N * K * sizeof(ReqHdr), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t.w.data(), c->d_sm_words.p, (size_t)N * DW * 8, hipMemcpyDeviceToHost));
+            }
+            for (int q = 0; q < N; q++)
+                if (t.tmpl[q] < 0 || t.tmpl[q] >= (int)c->tmpl_np.size() || t.ntypes[q] < 0 || t.ntypes[q] > (int)M)
+                    return fail(ctx, KP_E_DEVICE, "simulate_kernel: inconsistent NodeClaim record");
+        }
+    }
+    int64_t st[SS_COUNT];
+    HIPCHK(hipMemcpy(st, c->d_sm_stats.p, sizeof st, hipMemcpyDeviceToHost));
+    for (int i = 0; i < SS_COUNT; i++) c->sm_counts[i] += st[i];
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_simulate_execute(kp_ctx* ctx, int32_t mode, int32_t probe_begin, int32_t probe_end,
+                                         kp_sim_result* rows, int32_t cap_rows) try {
+    if (!ctx) return KP_E_INVALID;
+    if (const kp_status st = sim_check(ctx, "kp_simulate_execute", mode); st != KP_OK) return st;
+    const auto t0 = clk::now();
+    const int np = cons_probes(ctx, mode);
+    const int b0 = probe_begin > 0 ? probe_begin : 0;
+    const int b1 = probe_end > 0 && probe_end < np ? probe_end : np;
+    if (b0 > b1) return fail(ctx, KP_E_INVALID, "probe range outside the probe list");
+    const int n = b1 - b0;
+    sim_begin(ctx);
+    if (n > cap_rows || (n > 0 && !rows)) return fail(ctx, KP_E_BUFFER, "kp_simulate_execute: " + std::to_string(n) + " rows");
+    if (n == 0) return KP_OK;
+    if (const kp_status st = sim_run(ctx, mode, b0, b1, rows, nullptr); st != KP_OK) return st;
+    ctx->sm_ms[2] = ns_since(t0) * 1e-6;
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+// One probe with its details; the last probe's requirement digests stay with the ctx.
+static kp_status sim_one(kp_ctx* ctx, int mode, int probe, kp_sim_result& row, SimDetail& det) {
+    if (probe < 0 || probe >= cons_probes(ctx, mode)) return fail(ctx, KP_E_INVALID, "probe out of range");
+    return sim_run(ctx, mode, probe, probe + 1, &row, &det);
+}
+
+extern "C" kp_status kp_simulate_nodeclaims(kp_ctx* ctx, int32_t mode, int32_t probe, kp_sim_nodeclaims* out) try {
+    if (!ctx || !out) return KP_E_INVALID;
+    if (const kp_status st = sim_check(ctx, "kp_simulate_nodeclaims", mode); st != KP_OK) return st;
+    const auto t0 = clk::now();
+    kp_ctx* c = ctx;
+    sim_begin(c);
+    c->sm_last_n = 0;
+    out->row = kp_sim_result{};
+    out->n_nodeclaims = out->n_type_ids = out->n_pods = 0;
+    for (int i = 0; i < KP_SIM_MAX_NODECLAIMS; i++) {
+        out->nodeclaim_nodepool[i] = -1;
+        out->nodeclaim_n_pods[i] = out->nodeclaim_n_options[i] = 0;
+        out->nodeclaim_slice_pos[i] = -1;
+        out->nodeclaim_type_offset[i] = 0;
+    }
+    out->nodeclaim_type_offset[KP_SIM_MAX_NODECLAIMS] = 0;
+    SimDetail t;
+    if (const kp_status st = sim_one(ctx, mode, probe, out->row, t); st != KP_OK) return st;
+    c->sm_ms[2] = ns_since(t0) * 1e-6;
+    if (out->row.status != KP_SIM_OK) return KP_OK;
+    const int M = std::max(c->dev.M, 1), K = std::max(c->dev.K, 1), DW = std::max(c->dev.DW, 1);
+    const int N = t.n_nc;
+    // the probe's pods: the pending pods, then its candidates' reschedulable pods in candidate order
+    const std::vector<int32_t>& coff = c->cons_off;
+    const int c0 = mode == KP_CONSOLIDATE_SINGLE ? probe : 0, c1 = mode == KP_CONSOLIDATE_SINGLE ? probe + 1 : probe + 2;
+    const int npend = c->cons_n_pending, ncp = coff[c1] - coff[c0];
+    std::vector<int32_t> pods(npend + ncp);
+    if (npend) HIPCHK(hipMemcpy(pods.data(), c->d_pending.p, (size_t)npend * 4, hipMemcpyDeviceToHost));
+    if (ncp) HIPCHK(hipMemcpy(pods.data() + npend, c->d_cand_pods.p + coff[c0], (size_t)ncp * 4, hipMemcpyDeviceToHost));
+    int n_ids = 0;
+    for (int i = 0; i < N; i++) n_ids += t.ntypes[i];
+    out->n_nodeclaims = N;
+    out->n_type_ids = n_ids;
+    out->n_pods = (int)pods.size();
+    c->sm_last_n = N;
+    c->sm_last_h.assign(t.h.begin(), t.h.begin() + (size_t)N * K);
+    c->sm_last_w.assign(t.w.begin(), t.w.begin() + (size_t)N * DW);
+    if (n_ids > out->cap_type_ids || (int)pods.size() > out->cap_pods || (n_ids > 0 && !out->type_ids) ||
+        (!pods.empty() && (!out->pods || !out->pod_result || !out->pod_order)))
+        return fail(ctx, KP_E_BUFFER, "kp_simulate_nodeclaims: " + std::to_string(n_ids) + " type ids, " +
+                                          std::to_string(pods.size()) + " pods");
+    int off = 0;
+    for (int i = 0; i < N; i++) {
+        out->nodeclaim_nodepool[i] = t.valid[i] ? c->tmpl_np[t.tmpl[i]] : -1;
+        out->nodeclaim_n_pods[i] = t.npods[i];
+        out->nodeclaim_slice_pos[i] = t.spos[i];
+        out->nodeclaim_n_options[i] = t.nopts[i];
+        out->nodeclaim_type_offset[i] = off;
+        for (int q = 0; q < t.ntypes[i]; q++) out->type_ids[off++] = t.types[(size_t)i * M + q];
+    }
+    for (int i = N; i <= KP_SIM_MAX_NODECLAIMS; i++) out->nodeclaim_type_offset[i] = off;
+    std::unordered_map<int32_t, int32_t> at;
+    for (size_t i = 0; i < pods.size(); i++) {
+        at[pods[i]] = (int32_t)i;
+        out->pods[i] = pods[i];
+        out->pod_result[i] = KP_POD_UNSCHEDULABLE;
+        out->pod_order[i] = -1;
+    }
+    for (int e = 0; e < t.n_log; e++) {
+        const auto it = at.find(t.log[2 * e]);
+        const int res = t.log[2 * e + 1];
+        if (it == at.end() || res >= N) return fail(ctx, KP_E_DEVICE, "kp_simulate_nodeclaims: inconsistent placement log");
+        if (res >= 0 && !t.valid[res]) continue;  // a dropped NodeClaim's pods get errors
+        out->pod_result[it->second] = res;
+        out->pod_order[it->second] = e;
+    }
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_simulate_nodeclaim_requirements(kp_ctx* ctx, int32_t nc, char* buf, int64_t cap, int64_t* needed) try {
+    if (!ctx) return KP_E_INVALID;
+    if (!cons_explainable(ctx)) return fail(ctx, KP_E_STATE, "kp_simulate_nodeclaim_requirements without a prepared pass");
+    if (nc < 0 || nc >= ctx->sm_last_n) return fail(ctx, KP_E_INVALID, "nodeclaim index");
+    const int K = std::max(ctx->dev.K, 1), DW = std::max(ctx->dev.DW, 1);
+    const std::string s = reqs_text(ctx, ctx->sm_last_h.data() + (size_t)nc * K, ctx->sm_last_w.data() + (size_t)nc * DW);
+    if (needed) *needed = (int64_t)s.size() + 1;
+    if ((int64_t)s.size() + 1 > cap || !buf) return KP_E_BUFFER;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_drift_command(kp_ctx* ctx, kp_drift_command_out* out) try {
+    if (!ctx || !out) return KP_E_INVALID;
+    if (const kp_status st = sim_check(ctx, "kp_drift_command", KP_CONSOLIDATE_SINGLE); st != KP_OK) return st;
+    const auto t0 = clk::now();
+    kp_ctx* c = ctx;
+    sim_begin(c);
+    out->decision = KP_DRIFT_NONE;
+    out->n_candidates = out->n_nodeclaims = 0;
+    out->failed_candidate = -1;
+    out->row = kp_sim_result{};
+    const int NC = c->cons.n_cand;
+    const std::vector<int32_t>& coff = c->cons_off;
+    // the empty candidates need no scheduling simulation: the command is all of them
+    std::vector<int32_t> empty;
+    for (int i = 0; i < NC; i++)
+        if (coff[i + 1] == coff[i]) empty.push_back(i);
+    if (!empty.empty()) {
+        out->decision = KP_DRIFT_DELETE_EMPTY;
+        out->n_candidates = (int32_t)empty.size();
+        c->sm_ms[2] = ns_since(t0) * 1e-6;
+        if ((int)empty.size() > out->cap_candidates || !out->candidates)
+            return fail(ctx, KP_E_BUFFER, "kp_drift_command: " + std::to_string(empty.size()) + " candidates");
+        for (size_t i = 0; i < empty.size(); i++) out->candidates[i] = empty[i];
+        return KP_OK;
+    }
+    if (NC == 0) return KP_OK;
+    // every single-node probe in one pass, then drift's loop over the rows: the first candidate whose pods all land
+    std::vector<kp_sim_result> rows(NC);
+    if (const kp_status st = sim_run(ctx, KP_CONSOLIDATE_SINGLE, 0, NC, rows.data(), nullptr); st != KP_OK) return st;
+    c->sm_ms[2] = ns_since(t0) * 1e-6;
+    for (int i = 0; i < NC; i++) {
+        if (rows[i].status != KP_SIM_OK) {
+            out->failed_candidate = i;
+            return fail(ctx, KP_E_UNSUPPORTED,
+                        "kp_drift_command: candidate " + std::to_string(i) +
+                            (rows[i].status == KP_SIM_NODECLAIM_OVERFLOW ? " needs more than 12 NodeClaims"
+                                                                         : " is a probe the simulate kernel does not cover"));
+        }
+        if (!rows[i].all_scheduled) continue;  // core publishes a Blocked event and moves on
+        out->decision = KP_DRIFT_REPLACE;
+        out->n_candidates = 1;
+        out->n_nodeclaims = rows[i].n_new_nodeclaims;
+        out->row = rows[i];
+        if (out->cap_candidates < 1 || !out->candidates) return fail(ctx, KP_E_BUFFER, "kp_drift_command: 1 candidate");
+        out->candidates[0] = i;
+        return KP_OK;
+    }
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_consolidate_validate(kp_ctx* ctx, int32_t mode, int32_t probe, int32_t had_replacement,
+                                             int32_t n_type_ids, const int32_t* type_ids, int32_t* verdict) try {
+    if (!ctx || !verdict || n_type_ids < 0 || (n_type_ids > 0 && !type_ids)) return KP_E_INVALID;
+    if (const kp_status st = sim_check(ctx, "kp_consolidate_validate", mode); st != KP_OK) return st;
+    const auto t0 = clk::now();
+    kp_ctx* c = ctx;
+    sim_begin(c);
+    kp_sim_result row{};
+    SimDetail t;
+    if (const kp_status st = sim_one(ctx, mode, probe, row, t); st != KP_OK) return st;
+    c->sm_ms[2] = ns_since(t0) * 1e-6;
+    if (row.status != KP_SIM_OK)
+        return fail(ctx, KP_E_UNSUPPORTED, row.status == KP_SIM_NODECLAIM_OVERFLOW
+                                               ? "kp_consolidate_validate: the probe needs more than 12 NodeClaims"
+                                               : "kp_consolidate_validate: a probe the simulate kernel does not cover");
+    if (!row.all_scheduled) {
+        *verdict = KP_VALIDATE_PODS_UNSCHEDULABLE;
+    } else if (row.n_new_nodeclaims == 0) {
+        *verdict = had_replacement ? KP_VALIDATE_NO_NODECLAIM : KP_VALIDATE_VALID;
+    } else if (row.n_new_nodeclaims > 1) {
+        *verdict = KP_VALIDATE_MULTIPLE_NODECLAIMS;
+    } else if (!had_replacement) {
+        *verdict = KP_VALIDATE_NEEDS_NODECLAIM;
+    } else {
+        // instanceTypesAreSubset(command's options, the re-simulated NodeClaim's InstanceTypeOptions)
+        const int M = std::max(c->dev.M, 1);
+        int nc = -1;
+        for (int i = 0; i < t.n_nc; i++)
+            if (t.valid[i]) nc = i;
+        std::set<int32_t> have;
+        for (int q = 0; nc >= 0 && q < t.ntypes[nc]; q++) have.insert(t.types[(size_t)nc * M + q]);
+        bool sub = nc >= 0;
+        for (int i = 0; i < n_type_ids && sub; i++) sub = have.count(type_ids[i]) != 0;
+        *verdict = sub ? KP_VALIDATE_VALID : KP_VALIDATE_NOT_SUBSET;
+    }
+    return KP_OK;
+} catch (const std::exception& e) {
+    return fail(ctx, KP_E_INVALID, e.what());
+}
+
+extern "C" kp_status kp_simulate_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters) {
+    if (!ctx) return KP_E_INVALID;
+    if (ms)
+        for (int i = 0; i < 3; i++) ms[i] = ctx->sm_ms[i];
+    for (int i = 0; counters && i < n_counters && i < 6; i++) counters[i] = ctx->sm_counts[i];
     return KP_OK;
 }
 

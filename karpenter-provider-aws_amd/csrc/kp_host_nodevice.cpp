@@ -25,4 +25,31 @@ hipError_t kp_launch_consolidate_explain(const KpDev& d, const KpCons& k, const 
     if (x.n_rec) x.n_rec[0] = 0;
     return e;
 }
+
+// kp_simulate.hip's launchers: nothing is simulated, every probe reports an empty queue with everything scheduled and no
+// NodeClaim, except that in a pass with host ports or volume limits its MUT probes count as the probes the kernel does
+// not cover (the host layer's batching, row folding and decoding still run end to end).
+bool kp_sim_plan_lds(const KpDev&, KpSim& x, int) {
+    x.lds_bytes = 1024;
+    return true;
+}
+hipError_t kp_launch_simulate(const KpCons& k, const KpSim& x, hipStream_t, const KpDev* d_dev, const KpCons*,
+                              const KpSim*) {
+    for (int i = 0; i < k.n_probes; i++) {
+        x.rows[i] = KpSimRow{};
+        const int gp = k.probe0 + i;
+        if (k.mut && (d_dev->PW > 0 || d_dev->VD > 0) && (k.mode == KP_CONSOLIDATE_SINGLE ? k.mut_s[gp] : k.mut_m[gp]) != 0)
+            x.rows[i].status = KP_SIM_UNSUPPORTED_PROBE;
+        x.n_log[i] = 0;
+        for (int q = 0; q < KP_SIM_MAX_NODECLAIMS; q++) {
+            const size_t e = (size_t)q * k.n_probes + i;
+            x.nc_nonpend[e] = 0;
+            d_dev->nc_tmpl[e] = 0;
+            d_dev->nc_npods[e] = 0;
+            d_dev->nc_slice_pos[e] = -1;
+        }
+    }
+    x.stats[SS_PROBES] += k.n_probes;
+    return hipSuccess;
+}
 #endif

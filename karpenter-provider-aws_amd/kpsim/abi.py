@@ -240,6 +240,42 @@ PROBE_EXPLANATION_DTYPE = np.dtype([("reason", np.int32), ("flags", np.int32), (
 assert PROBE_EXPLANATION_DTYPE.itemsize == C.sizeof(kp_probe_explanation)
 
 
+# kp_simulate_*: SimulateScheduling results of a probe (kpsim.h KP_SIM_*, kp_sim_result, kp_sim_nodeclaims)
+KP_SIM_MAX_NODECLAIMS = 12
+KP_SIM_OK, KP_SIM_NODECLAIM_OVERFLOW, KP_SIM_UNSUPPORTED_PROBE = range(3)
+KP_DRIFT_NONE, KP_DRIFT_DELETE_EMPTY, KP_DRIFT_REPLACE = range(3)
+(KP_VALIDATE_VALID, KP_VALIDATE_PODS_UNSCHEDULABLE, KP_VALIDATE_NO_NODECLAIM, KP_VALIDATE_MULTIPLE_NODECLAIMS,
+ KP_VALIDATE_NEEDS_NODECLAIM, KP_VALIDATE_NOT_SUBSET) = range(6)
+VALIDATE_NAMES = ["VALID", "PODS_UNSCHEDULABLE", "NO_NODECLAIM", "MULTIPLE_NODECLAIMS", "NEEDS_NODECLAIM", "NOT_SUBSET"]
+
+
+class kp_sim_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("all_scheduled", C.c_int32), ("n_new_nodeclaims", C.c_int32),
+                ("n_dropped", C.c_int32), ("n_pods", C.c_int32), ("n_unscheduled", C.c_int32)]
+
+
+SIM_DTYPE = np.dtype([("status", np.int32), ("all_scheduled", np.int32), ("n_new_nodeclaims", np.int32),
+                      ("n_dropped", np.int32), ("n_pods", np.int32), ("n_unscheduled", np.int32)])
+assert SIM_DTYPE.itemsize == C.sizeof(kp_sim_result)
+
+
+class kp_sim_nodeclaims(C.Structure):
+    _fields_ = [("cap_type_ids", C.c_int32), ("type_ids", c_int32_p), ("cap_pods", C.c_int32), ("pods", c_int32_p),
+                ("pod_result", c_int32_p), ("pod_order", c_int32_p), ("row", kp_sim_result),
+                ("n_nodeclaims", C.c_int32), ("n_type_ids", C.c_int32), ("n_pods", C.c_int32),
+                ("nodeclaim_nodepool", C.c_int32 * KP_SIM_MAX_NODECLAIMS),
+                ("nodeclaim_n_pods", C.c_int32 * KP_SIM_MAX_NODECLAIMS),
+                ("nodeclaim_slice_pos", C.c_int32 * KP_SIM_MAX_NODECLAIMS),
+                ("nodeclaim_n_options", C.c_int32 * KP_SIM_MAX_NODECLAIMS),
+                ("nodeclaim_type_offset", C.c_int32 * (KP_SIM_MAX_NODECLAIMS + 1))]
+
+
+class kp_drift_command_out(C.Structure):
+    _fields_ = [("cap_candidates", C.c_int32), ("candidates", c_int32_p), ("decision", C.c_int32),
+                ("n_candidates", C.c_int32), ("n_nodeclaims", C.c_int32), ("failed_candidate", C.c_int32),
+                ("row", kp_sim_result)]
+
+
 KP_FILTER_NAMES = ["compatible-available-filter", "capacity-reservation-type-filter", "capacity-block-filter",
                    "reserved-offering-filter", "exotic-instance-filter", "spot-instance-filter"]  # filter.go Name()
 KP_N_FILTERS = 6

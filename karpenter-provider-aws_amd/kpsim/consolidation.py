@@ -66,6 +66,18 @@ def command_call(fn, cap_types=1024, cap_req=1 << 16):
     return st, cmd
 
 
+def validate_command(ctx, cmd: Command) -> int:
+    """ValidateCommand's tail ([core] disruption/validation.go, recalled) for a Command kp_consolidate_command /
+    kp_consolidate_replacement produced, over the pass ctx holds now (prepare the cluster as it is at validation time
+    first): re-simulates the command's probe and returns abi.KP_VALIDATE_* (kp_consolidate_validate).  A NO_OP command
+    has nothing to validate."""
+    if cmd.decision == abi.KP_DECISION_NONE:
+        raise ValueError("no command to validate")
+    if cmd.mode not in (abi.KP_CONSOLIDATE_SINGLE, abi.KP_CONSOLIDATE_MULTI) or cmd.probe < 0:
+        raise ValueError("the command does not name its probe")
+    return ctx.consolidate_validate(cmd.mode, cmd.probe, cmd.decision == abi.KP_DECISION_REPLACE, cmd.type_ids)
+
+
 def first_valid_single(results: np.ndarray, probe0: int = 0) -> int:
     """Index (global probe id) of the first non-NONE single-node probe, or -1."""
     idx = np.nonzero(results["decision"] != abi.KP_DECISION_NONE)[0]

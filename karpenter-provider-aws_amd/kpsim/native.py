@@ -16,6 +16,8 @@ EXPORTS = [
     "kp_catalog_free", "kp_consolidate_command", "kp_consolidate_replacement", "kp_solve_volume_encoding",
     "kp_solve_explain", "kp_solve_explain_key", "kp_solve_explain_stats", "kp_consolidate_explain",
     "kp_consolidate_explain_pods", "kp_consolidate_explain_key", "kp_consolidate_explain_stats",
+    "kp_simulate_execute", "kp_simulate_nodeclaims", "kp_simulate_nodeclaim_requirements", "kp_drift_command",
+    "kp_consolidate_validate", "kp_simulate_stats",
 ]
 
 _lib = None
@@ -75,6 +77,16 @@ def load():
                                                   C.POINTER(abi.kp_pod_explanation), C.c_int64, C.POINTER(C.c_int64)]
         L.kp_consolidate_explain_key.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
         L.kp_consolidate_explain_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
+    if hasattr(L, "kp_simulate_execute"):  # (absent from older libraries, A/B only)
+        L.kp_simulate_execute.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(abi.kp_sim_result),
+                                          C.c_int32]
+        L.kp_simulate_nodeclaims.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.kp_sim_nodeclaims)]
+        L.kp_simulate_nodeclaim_requirements.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64,
+                                                         C.POINTER(C.c_int64)]
+        L.kp_drift_command.argtypes = [C.c_void_p, C.POINTER(abi.kp_drift_command_out)]
+        L.kp_consolidate_validate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.kp_simulate_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
     L.kp_launch_select.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.kp_launch_request), C.c_int32,
                                    C.POINTER(abi.kp_launch_result), C.POINTER(C.c_int32), C.c_int32,
                                    C.POINTER(C.c_int32), C.c_int32]
@@ -357,6 +369,92 @@ class Context:
         ms = (C.c_double * 2)()
         ct = (C.c_int64 * 2)()
         self.check(self.L.kp_consolidate_explain_stats(self.h, ms, ct, 2), "kp_consolidate_explain_stats")
+        return list(ms), list(ct)
+
+    def simulate_execute(self, mode, n_probes, begin=0, end=0):
+        """kp_simulate_execute: SimulateScheduling's Results of probes [begin, end) of `mode` (SINGLE or MULTI) of the
+        prepared pass, with up to 12 new NodeClaims -> numpy array of abi.SIM_DTYPE; n_probes = the mode's probe count."""
+        import numpy as np
+        b1 = end if 0 < end < n_probes else n_probes
+        out = np.zeros(max(1, b1 - begin), abi.SIM_DTYPE)
+        self.check(self.L.kp_simulate_execute(self.h, mode, begin, end, out.ctypes.data_as(C.POINTER(abi.kp_sim_result)),
+                                              len(out)), "kp_simulate_execute")
+        return out[:max(0, b1 - begin)]
+
+    def simulate_nodeclaims(self, mode, probe):
+        """kp_simulate_nodeclaims of one probe -> (row dict, pods, model.Results, requirements): pods lists the probe's
+        pods (pending first, then its candidates' pods) as indices into cluster.pods, the Results' pod arrays follow that
+        list (an existing node is -2 - j, j into cluster.existing), requirements[i] is NodeClaim i's parsed
+        requirements.  A row that is not KP_SIM_OK comes with no pods and no NodeClaims."""
+        import numpy as np
+        from kpsim import model
+        cap_t, cap_p = 1024, 1024
+        for _ in range(2):
+            arr = {k: np.full(max(1, n), -7, np.int32) for k, n in
+                   (("type_ids", cap_t), ("pods", cap_p), ("pod_result", cap_p), ("pod_order", cap_p))}
+            o = abi.kp_sim_nodeclaims()
+            o.cap_type_ids, o.cap_pods = cap_t, cap_p
+            for k, a in arr.items():
+                setattr(o, k, a.ctypes.data_as(abi.c_int32_p))
+            st = self.L.kp_simulate_nodeclaims(self.h, mode, probe, C.byref(o))
+            if st != abi.KP_E_BUFFER:
+                break
+            cap_t, cap_p = max(cap_t, o.n_type_ids), max(cap_p, o.n_pods)
+        self.check(st, "kp_simulate_nodeclaims")
+        n, m = o.n_nodeclaims, o.n_pods
+        off = list(o.nodeclaim_type_offset)
+        res = model.Results(np.array(o.nodeclaim_nodepool[:n], np.int32), np.array(o.nodeclaim_n_pods[:n], np.int32),
+                            np.array(o.nodeclaim_slice_pos[:n], np.int32), np.array(o.nodeclaim_n_options[:n], np.int32),
+                            [arr["type_ids"][off[i]:off[i + 1]].tolist() for i in range(n)],
+                            arr["pod_result"][:m].copy(), arr["pod_order"][:m].copy(), {})
+        reqs = [model.parse_requirements_blob(self.simulate_nodeclaim_requirements(i)) for i in range(n)]
+        row = {f: int(getattr(o.row, f)) for f, _ in abi.kp_sim_result._fields_}
+        return row, arr["pods"][:m].copy(), res, reqs
+
+    def simulate_nodeclaim_requirements(self, nc):
+        need = C.c_int64(0)
+        buf = C.create_string_buffer(1 << 16)
+        st = self.L.kp_simulate_nodeclaim_requirements(self.h, nc, buf, len(buf), C.byref(need))
+        if st == abi.KP_E_BUFFER:
+            buf = C.create_string_buffer(need.value)
+            st = self.L.kp_simulate_nodeclaim_requirements(self.h, nc, buf, len(buf), C.byref(need))
+        self.check(st, "kp_simulate_nodeclaim_requirements")
+        return buf.value.decode()
+
+    def drift_command(self, cap_candidates=4096):
+        """kp_drift_command over the prepared candidates -> dict(decision, candidates, n_nodeclaims, row); a REPLACE's
+        NodeClaims are read with simulate_nodeclaims(KP_CONSOLIDATE_SINGLE, candidates[0])."""
+        import numpy as np
+        for _ in range(2):
+            cands = np.zeros(max(1, cap_candidates), np.int32)
+            o = abi.kp_drift_command_out()
+            o.cap_candidates = len(cands)
+            o.candidates = cands.ctypes.data_as(abi.c_int32_p)
+            st = self.L.kp_drift_command(self.h, C.byref(o))
+            if st != abi.KP_E_BUFFER:
+                break
+            cap_candidates = max(cap_candidates, o.n_candidates)
+        self.check(st, "kp_drift_command")
+        return dict(decision=int(o.decision), candidates=[int(x) for x in cands[:o.n_candidates]],
+                    n_nodeclaims=int(o.n_nodeclaims),
+                    row={f: int(getattr(o.row, f)) for f, _ in abi.kp_sim_result._fields_})
+
+    def consolidate_validate(self, mode, probe, had_replacement, type_ids=()):
+        """kp_consolidate_validate: ValidateCommand's verdict (abi.KP_VALIDATE_*) for the command of one probe."""
+        import numpy as np
+        t = np.ascontiguousarray(type_ids, np.int32)
+        v = C.c_int32(-1)
+        self.check(self.L.kp_consolidate_validate(self.h, mode, probe, 1 if had_replacement else 0, len(t),
+                                                  t.ctypes.data_as(abi.c_int32_p) if len(t) else None, C.byref(v)),
+                   "kp_consolidate_validate")
+        return int(v.value)
+
+    def simulate_stats(self):
+        """(ms[simulate kernel, finalize kernel, whole call], counters[pods popped, NodeClaim evaluations, template
+        evaluations, probes run, overflow rows, unsupported rows]) of the last simulate / drift / validate call."""
+        ms = (C.c_double * 3)()
+        ct = (C.c_int64 * 6)()
+        self.check(self.L.kp_simulate_stats(self.h, ms, ct, 6), "kp_simulate_stats")
         return list(ms), list(ct)
 
     def close(self):
