@@ -1042,8 +1042,9 @@ kp_status kp_consolidate_validate(kp_ctx* ctx, int32_t mode, int32_t probe, int3
                                   const int32_t* type_ids, int32_t* verdict);
 
 /* The last simulate / drift / validate call: ms[3] = {simulate_kernel, finalize_kernel (HIP events, summed over the
- * call's batches), whole call}; counters[6] = {pods popped, NodeClaim evaluations, template evaluations, probes run,
- * KP_SIM_NODECLAIM_OVERFLOW rows, KP_SIM_UNSUPPORTED_PROBE rows}.  n_counters up to 6. */
+ * call's batches), whole call}; counters[7] = {pods popped, NodeClaim evaluations, template evaluations, probes run,
+ * KP_SIM_NODECLAIM_OVERFLOW rows, KP_SIM_UNSUPPORTED_PROBE rows, batches (launches of simulate_kernel)}.  n_counters up
+ * to 7. */
 kp_status kp_simulate_stats(kp_ctx* ctx, double* ms, int64_t* counters, int32_t n_counters);
 
 #ifdef __cplusplus

@@ -646,7 +646,7 @@ struct kp_ctx {
     DBuf<KpSim> d_sm_x;
     hipEvent_t smev[3] = {};
     double sm_ms[3] = {};
-    int64_t sm_counts[6] = {};
+    int64_t sm_counts[7] = {};
     int sm_last_n = 0;                       // NodeClaims of the last kp_simulate_nodeclaims
     std::vector<ReqHdr> sm_last_h;           // [sm_last_n][K]
     std::vector<uint64_t> sm_last_w;         // [sm_last_n][DW]
@@ -5293,7 +5293,9 @@ static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* r
     const size_t per = NCM * (K * sizeof(ReqHdr) + DW * 8 + TW * 8 + R * 8 + M * 4 + 40) + (size_t)k.ring_cap * 16 +
                        A * E * 8 + (size_t)k.PW * 8 +
                        (k.mut ? E * 4 + (size_t)x.ov_cap * (K * sizeof(ReqHdr) + DW * 8) : 0);
-    const int W = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)64 << 20) / per)));
+    int W = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)64 << 20) / per)));
+    if (const char* e = getenv("KPSIM_SIM_BATCH"))  // diagnostics: KPSIM_SIM_BATCH=n runs at most n probes per batch
+        if (atoi(e) >= 1) W = std::min(W, atoi(e));
     const size_t WN = (size_t)W * NCM;
     if (c->d_sm_hdr.n < WN * K) {
         HIPCHK(c->d_sm_hdr.ensure(WN * K));
@@ -5382,6 +5384,7 @@ static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* r
         k.n_probes = nb;
         k.probe0 = q0;
         d.NCcap = count;
+        c->sm_counts[6]++;
         HIPCHK(hipMemcpyAsync(c->d_sm_count.p, &count, sizeof count, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(c->d_sm_dev.p, &d, sizeof(KpDev), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(c->d_sm_k.p, &k, sizeof(KpCons), hipMemcpyHostToDevice, s));
@@ -5682,7 +5685,7 @@ extern "C" kp_status kp_simulate_stats(kp_ctx* ctx, double* ms, int64_t* counter
     if (!ctx) return KP_E_INVALID;
     if (ms)
         for (int i = 0; i < 3; i++) ms[i] = ctx->sm_ms[i];
-    for (int i = 0; counters && i < n_counters && i < 6; i++) counters[i] = ctx->sm_counts[i];
+    for (int i = 0; counters && i < n_counters && i < 7; i++) counters[i] = ctx->sm_counts[i];
     return KP_OK;
 }
 

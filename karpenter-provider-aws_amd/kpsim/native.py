@@ -451,10 +451,10 @@ class Context:
 
     def simulate_stats(self):
         """(ms[simulate kernel, finalize kernel, whole call], counters[pods popped, NodeClaim evaluations, template
-        evaluations, probes run, overflow rows, unsupported rows]) of the last simulate / drift / validate call."""
+        evaluations, probes run, overflow rows, unsupported rows, batches]) of the last simulate / drift / validate call."""
         ms = (C.c_double * 3)()
-        ct = (C.c_int64 * 6)()
-        self.check(self.L.kp_simulate_stats(self.h, ms, ct, 6), "kp_simulate_stats")
+        ct = (C.c_int64 * 7)()
+        self.check(self.L.kp_simulate_stats(self.h, ms, ct, 7), "kp_simulate_stats")
         return list(ms), list(ct)
 
     def close(self):

@@ -263,3 +263,83 @@ def drift_case(cat, with_empty=False, movable=True):
         owner.append([])
     prob = model.Problem(cat, [pool], classes, synth.pods_from_specs(specs), existing=nodes)
     return model.ConsolidationProblem(prob, [_cand(i, p, t0) for i, p in enumerate(owner)])
+
+
+# counts of the base pods per group, chosen by running tests/test_simulate_cpu.py::test_ladder_cases: each solves to
+# exactly len(counts) NodeClaims, the final slice order is not the identity, and the floaters' destinations depend on
+# both the stable sort's tie rule and the slice order.  LADDER_TIES: every count equal, so every comparison is a tie.
+LADDERS = {"n12": [5, 3, 4, 1, 2, 6, 1, 3, 2, 4, 1, 2], "n9": [2, 2, 1, 3, 1, 1, 2, 3, 1], "n7": [1, 2, 3, 1, 2, 3, 1],
+           "n12_ties": [2] * 12}
+LADDER_FLOATERS = 14
+
+
+def ladder_types(cat, n):
+    """n distinct catalog rows with an on-demand offering and 16 or more cpu, of one architecture"""
+    cpu = model.RIDX["cpu"]
+    arch = _arch(cat[small_type(cat)])
+    rows_ = [t for t, it in enumerate(cat) if _has(it, "on-demand") and it.allocatable[cpu] >= 16000 and _arch(it) == arch][:n]
+    assert len(rows_) == n
+    return rows_
+
+
+def ladder_case(cat, counts, n_floaters=LADDER_FLOATERS, seed=0):
+    """len(counts) NodeClaims whose sort.Slice order decides where pods go (slice_order_case at 7 to 12 elements).
+    Group g's counts[g] base pods select instance type t_g alone (cpu 0.6 to 1.0, all different, so the queue interleaves
+    the groups); then n_floaters pods with smaller requests, each selecting 2 to 4 of the types, are popped after every
+    base pod and join the first compatible NodeClaim of the slice, which is re-sorted by pod count after every placement.
+    One existing node without cpu left, one candidate owning every pod.
+    -> (ConsolidationProblem, types per group, [(pod, groups it lists)] of the floaters)"""
+    from kpsim import synth
+    from kpsim.model import INSTANCE_TYPE, PodClass, Requirement
+    n = len(counts)
+    rng = np.random.Generator(np.random.PCG64(8100 + seed))
+    t0 = small_type(cat)
+    types = ladder_types(cat, n)
+    classes = [PodClass([Requirement(INSTANCE_TYPE, "In", [cat[t].name])]) for t in types]
+    base = [(g, j) for g in range(n) for j in range(counts[g])]
+    cpus = rng.permutation(np.arange(600, 1001))[:len(base)]  # distinct millicpu values
+    specs = [(g, {"cpu": "%dm" % int(c)}) for (g, _), c in zip(base, cpus)]
+    floaters = []
+    for f in range(n_floaters):
+        groups = sorted(int(g) for g in rng.choice(n, size=int(rng.integers(2, 5)), replace=False))
+        classes.append(PodClass([Requirement(INSTANCE_TYPE, "In", [cat[types[g]].name for g in groups])]))
+        floaters.append((len(specs), groups))
+        specs.append((len(classes) - 1, {"cpu": "%dm" % (500 - 20 * f)}))
+    prob = model.Problem(cat, [synth.default_nodepool()], classes, synth.pods_from_specs(specs),
+                         existing=[_node("n0", cat[t0], cpu_avail=0)])
+    return model.ConsolidationProblem(prob, [_cand(0, list(range(len(specs))), t0)]), types, floaters
+
+
+# queue ranks of bitmap_block_case's pods: both sides of every 64-bit word edge around the 4096-pod wave step
+BITMAP_CAND_RANKS = [0, 63, 64, 4095, 4096, 4097, 4159, 4160, -1]
+BITMAP_PEND_RANKS = [62, 4093, 4099]
+# fuzzgen seeds picked by running tests/test_simulate_cpu.py::test_bitmap_block_case: in both, probes create up to 6
+# NodeClaims and place pods on existing nodes; in the second some pods stay unscheduled (the queue cycles)
+BITMAP_SEEDS = [7608, 7632]
+
+
+def bitmap_block_case(cat, seed=BITMAP_SEEDS[0]):
+    """A pass over more than 4096 pods (the queue bitmap has more than 64 words, the kernel's scan takes a second wave
+    step) in which only the pods at chosen queue ranks take part: the candidates' pods at ranks BITMAP_CAND_RANKS (-1: the
+    last) plus a few around them, dealt round-robin to 4 candidates; pending pods at BITMAP_PEND_RANKS; every other pod
+    belongs to nobody.  The nodes keep little cpu, so pods open NodeClaims as well as land on nodes.
+    -> (ConsolidationProblem, rank of each pod)"""
+    import fuzzgen
+    cp = fuzzgen.fuzz_consolidation(cat, seed, n_nodes=24, n_pods=4300, n_candidates=4)
+    prob = cp.cluster
+    P = prob.pods.n
+    order = sorted(range(P), key=lambda p: cxr.queue_key(prob, p))
+    rank = np.empty(P, np.int64)
+    rank[order] = np.arange(P)
+    want = [r % P for r in BITMAP_CAND_RANKS] + [1, 65, 2047, 4094, 4098, 4161, P - 2]
+    owned = [[] for _ in cp.candidates]
+    for i, r in enumerate(want):
+        owned[i % len(owned)].append(order[r])
+    for c, pods in zip(cp.candidates, owned):
+        c.pods = np.array(sorted(pods), np.int32)
+    cp.pending = np.array(sorted(order[r] for r in BITMAP_PEND_RANKS), np.int32)
+    cpu = model.RIDX["cpu"]
+    for j, node in enumerate(prob.existing):  # every third node keeps one small pod's worth of cpu, the others none
+        node.available = node.available.copy()
+        node.available[cpu] = min(int(node.available[cpu]), 300 if j % 3 == 0 else 0)
+    return cp, rank

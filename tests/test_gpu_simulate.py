@@ -60,13 +60,37 @@ def check_probe(ctx, cp, mode, i, ref=None):
     return ref
 
 
-def check_pass(ctx, cp, every=3):
+_REFS = {}
+
+
+def cached_ref(key, cp, mode, i):
+    """sim_ref.reference(cp, mode, i), computed once per module for the cluster named `key` (name and whatever else
+    tells it from the others: the minValues policy, a seed); nothing changes a cached reference."""
+    k = (key, mode, i)
+    if k not in _REFS:
+        _REFS[k] = sim_ref.reference(cp, mode, i)
+    return _REFS[k]
+
+
+def cached_refs(key, cp, mode):
+    return [cached_ref(key, cp, mode, i) for i in range(sim_ref.n_probes(cp, mode))]
+
+
+def batch_cap(monkeypatch, cap):
+    """KPSIM_SIM_BATCH for the calls that follow (the host reads it on every call); None: unset"""
+    if cap is None:
+        monkeypatch.delenv("KPSIM_SIM_BATCH", raising=False)
+    else:
+        monkeypatch.setenv("KPSIM_SIM_BATCH", str(cap))
+
+
+def check_pass(ctx, cp, every=3, key=None):
     """Both probe lists of a prepared pass: every row, and the Results of every probe with 2 or more NodeClaims and of
-    every `every`-th other one."""
+    every `every`-th other one.  key: the cluster's name in the reference cache, if it has one."""
     n_over = n_rows = 0
     for mode in (SINGLE, MULTI):
         n = sim_ref.n_probes(cp, mode)
-        refs = [sim_ref.reference(cp, mode, i) for i in range(n)]
+        refs = cached_refs(key, cp, mode) if key else [sim_ref.reference(cp, mode, i) for i in range(n)]
         dev = ctx.simulate_execute(mode, n)
         sim_ref.assert_rows_equal(dev, sim_ref.rows(cp, mode, refs))
         for i, ref in enumerate(refs):
@@ -85,7 +109,7 @@ def check_pass(ctx, cp, every=3):
 def test_fuzz(ctx, corpora, name, policy):
     cp = corpora[policy][name]
     prepare(ctx, cp)
-    check_pass(ctx, cp)
+    check_pass(ctx, cp, key=(name, policy))
 
 
 def test_fuzz_overflow_share(ctx, corpora):
@@ -245,7 +269,7 @@ def test_drift_empty_candidates_need_no_simulation(ctx, cat):
     prepare(ctx, cp)
     cmd = ctx.drift_command()
     assert (cmd["decision"], cmd["candidates"], cmd["n_nodeclaims"]) == (abi.KP_DRIFT_DELETE_EMPTY, [4], 0)
-    assert ctx.simulate_stats()[1] == [0] * 6  # nothing was simulated
+    assert ctx.simulate_stats()[1] == [0] * 7  # nothing was simulated
 
 
 def test_drift_nothing_can_move(ctx, cat):
@@ -260,12 +284,13 @@ def test_drift_fuzz(ctx, corpora, name):
     cp = corpora[STRICT][name]
     prepare(ctx, cp)
     cmd = ctx.drift_command()
-    rows = sim_ref.rows(cp, SINGLE)
+    refs = cached_refs((name, STRICT), cp, SINGLE)
+    rows = sim_ref.rows(cp, SINGLE, refs)
     decision, cands = sim_ref.drift_replay(cp, rows)
     assert (cmd["decision"], cmd["candidates"]) == (decision, cands)
     if decision == abi.KP_DRIFT_REPLACE:
         assert cmd["n_nodeclaims"] == rows[cands[0]]["n_new_nodeclaims"]
-        check_probe(ctx, cp, SINGLE, cands[0])
+        check_probe(ctx, cp, SINGLE, cands[0], refs[cands[0]])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -435,3 +460,207 @@ def test_stats(ctx, corpora):
     ms, ct = ctx.simulate_stats()
     assert ms[0] > 0 and ms[1] > 0 and ms[2] >= ms[0] + ms[1]
     assert ct[3] == n and ct[0] >= sum(len(c.pods) for c in cp.candidates) and ct[2] > 0
+
+
+# ------------------------------------------------------------------------------------------------
+# more than one batch (KPSIM_SIM_BATCH caps the probes per batch; counter 6 of kp_simulate_stats counts the batches)
+# ------------------------------------------------------------------------------------------------
+# (cluster, mode, policy, caps); tests/test_simulate_cpu.py::test_batch_lists pins the NodeClaim counts per probe:
+#   fuzz5 MULTI   4 7 7 9 11 O O (O: past 12)  caps 1, 2: a last batch of overflow rows alone; 3: a short last batch
+#   fuzz9 MULTI   7 7 7 12 O                   cap 2: `most` 7, then 12; cap 4: the overflow row alone in the last batch
+#   min126 MULTI  0, 1 (1 dropped), 8 (7 dropped), 9 (8 dropped): dropped NodeClaims past the first batch
+#   fuzz4         22 MULTI probes from 2 to 8 NodeClaims, 23 SINGLE probes: `most` differs from batch to batch
+#   min6 SINGLE   no NodeClaim among the first five probes: a first batch with nothing to finalize
+BATCH_LISTS = [("fuzz5", MULTI, STRICT, (1, 2, 3)), ("fuzz9", MULTI, STRICT, (2, 4)), ("min126", MULTI, STRICT, (2, 3)),
+               ("min126", MULTI, BEST_EFFORT, (2, 3)), ("fuzz4", MULTI, STRICT, (5, 7, 21)),
+               ("fuzz4", SINGLE, STRICT, (5, 7, 21)), ("min6", SINGLE, STRICT, (5,))]
+CS_MUT = 17  # kp_consolidate_stats: probes the MUT variant ran
+
+
+def _batches(n, cap):
+    return -(-n // cap)
+
+
+@pytest.mark.parametrize("name,mode,policy,caps", BATCH_LISTS,
+                         ids=["%s-%s-%d" % (b[0], "multi" if b[1] == MULTI else "single", b[2]) for b in BATCH_LISTS])
+def test_batches(ctx, corpora, monkeypatch, name, mode, policy, caps):
+    """A probe list in several batches gives the rows of the reference, byte for byte those of one batch, and the same
+    counters; the consolidation pass's rows and figures are untouched."""
+    cp = corpora[policy][name]
+    prepare(ctx, cp)
+    n = sim_ref.n_probes(cp, mode)
+    want = sim_ref.rows(cp, mode, cached_refs((name, policy), cp, mode))
+    before = ctx.consolidate_execute(mode, n)
+    cstats = ctx.consolidate_stats()
+    batch_cap(monkeypatch, None)
+    whole = ctx.simulate_execute(mode, n)
+    st0 = ctx.simulate_stats()[1]
+    sim_ref.assert_rows_equal(whole, want)
+    assert st0[3] == n and st0[6] == 1
+    for cap in caps:
+        batch_cap(monkeypatch, cap)
+        got = ctx.simulate_execute(mode, n)
+        st = ctx.simulate_stats()[1]
+        print("%s mode %d cap %d: counters %s" % (name, mode, cap, st))
+        sim_ref.assert_rows_equal(got, want)
+        assert got.tobytes() == whole.tobytes()
+        assert st[:6] == st0[:6]
+        assert st[6] == _batches(n, cap) and st[6] > 1
+    batch_cap(monkeypatch, None)
+    assert ctx.simulate_execute(mode, n).tobytes() == whole.tobytes()
+    assert ctx.simulate_stats()[1] == st0
+    assert ctx.consolidate_stats() == cstats
+    assert ctx.consolidate_execute(mode, n).tobytes() == before.tobytes()
+
+
+def test_batch_lists_hold_mut_probes(ctx, corpora):
+    """At least two of test_batches' passes run probes with per-probe node requirement copies (kp_cons.h MUT)."""
+    with_mut = []
+    for name, mode, policy, _ in BATCH_LISTS:
+        cp = corpora[policy][name]
+        prepare(ctx, cp)
+        ctx.consolidate_execute(mode, sim_ref.n_probes(cp, mode))
+        if ctx.consolidate_stats()[1][CS_MUT] > 0:
+            with_mut.append((name, mode, policy))
+    print("passes with MUT probes:", with_mut)
+    assert len(with_mut) >= 2
+
+
+@pytest.mark.parametrize("name", ["fuzz5", "fuzz9"])
+def test_nodeclaims_after_capped_and_uncapped_calls(ctx, corpora, monkeypatch, name):
+    """The workers' slabs are strided by the batch's size and zeroed only when they grow: whole lists in one batch, lists
+    in batches of 3 and single probes (a batch of one) alternate over the same buffers, and every result stays right."""
+    cp = corpora[STRICT][name]
+    prepare(ctx, cp)
+    refs = {m: cached_refs((name, STRICT), cp, m) for m in (SINGLE, MULTI)}
+    want = {m: sim_ref.rows(cp, m, refs[m]) for m in (SINGLE, MULTI)}
+
+    def lists(cap):
+        batch_cap(monkeypatch, cap)
+        for m in (SINGLE, MULTI):
+            sim_ref.assert_rows_equal(ctx.simulate_execute(m, len(refs[m])), want[m])
+            assert ctx.simulate_stats()[1][6] == (_batches(len(refs[m]), cap) if cap else 1)
+        batch_cap(monkeypatch, None)
+
+    big = next(i for i, r in enumerate(refs[MULTI]) if r["row"]["status"] == abi.KP_SIM_OK and r["n_nodeclaims"] >= 7)
+    last = len(refs[MULTI]) - 1
+    assert refs[MULTI][last]["row"]["status"] == abi.KP_SIM_NODECLAIM_OVERFLOW
+    for _ in range(2):
+        lists(None)
+        lists(3)
+        for i in (big, last):
+            check_probe(ctx, cp, MULTI, i, refs[MULTI][i])
+            lists(None)
+    batch_cap(monkeypatch, 3)  # a single probe is a batch of one whatever the cap
+    check_probe(ctx, cp, MULTI, big, refs[MULTI][big])
+    assert ctx.simulate_stats()[1][6] == 1
+
+
+# ------------------------------------------------------------------------------------------------
+# sub-ranges of the probe lists
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cap", [None, 3])
+@pytest.mark.parametrize("mode", [SINGLE, MULTI])
+@pytest.mark.parametrize("name", ["fuzz4", "fuzz5"])
+def test_sub_ranges(ctx, corpora, monkeypatch, name, mode, cap):
+    """simulate_execute(mode, n, begin, end) is the whole list's rows [begin, end): ranges that start past 0, end before
+    the list does, hold one probe or none; a begin past the end is refused."""
+    cp = corpora[STRICT][name]
+    prepare(ctx, cp)
+    n = sim_ref.n_probes(cp, mode)
+    want = sim_ref.rows(cp, mode, cached_refs((name, STRICT), cp, mode))
+    batch_cap(monkeypatch, None)
+    whole = ctx.simulate_execute(mode, n)
+    sim_ref.assert_rows_equal(whole, want)
+    batch_cap(monkeypatch, cap)
+    mid = n // 2
+    parts = [(0, 2), (2, n - 2), (n - 2, n)]
+    assert 2 < mid < n - 2
+    for b, e in parts + [(1, n), (mid, mid + 1), (3, n - 2), (mid, mid), (n - 1, n)]:
+        got = ctx.simulate_execute(mode, n, begin=b, end=e)
+        st = ctx.simulate_stats()[1]
+        assert len(got) == e - b and got.tobytes() == whole[b:e].tobytes(), (b, e)
+        sim_ref.assert_rows_equal(got, want[b:e])
+        if b == e:
+            assert st == [0] * 7  # KP_OK, no rows, nothing simulated
+        else:
+            assert st[3] == e - b and st[6] == (_batches(e - b, cap) if cap else 1), (b, e, st)
+    assert b"".join(ctx.simulate_execute(mode, n, begin=b, end=e).tobytes() for b, e in parts) == whole.tobytes()
+    _raises(abi.KP_E_INVALID, ctx.simulate_execute, mode, n, mid, mid - 1)
+    _raises(abi.KP_E_INVALID, ctx.simulate_execute, mode, n, n - 1, 1)
+
+
+# ------------------------------------------------------------------------------------------------
+# drift over more candidates than one batch holds
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["fuzz1", "fuzz3", "fuzz5", "fuzz6", "fuzz8", "fuzz9", "drift_case"])
+def test_drift_under_a_batch_cap(ctx, corpora, cat, monkeypatch, name):
+    cp = sim_ref.drift_case(cat) if name == "drift_case" else corpora[STRICT][name]
+    prepare(ctx, cp)
+    NC = len(cp.candidates)
+    refs = cached_refs((name, STRICT), cp, SINGLE)
+    rows = sim_ref.rows(cp, SINGLE, refs)
+    decision, cands = sim_ref.drift_replay(cp, rows)
+    batch_cap(monkeypatch, None)
+    whole = ctx.drift_command()
+    assert ctx.simulate_stats()[1][6] == (0 if decision == abi.KP_DRIFT_DELETE_EMPTY else 1)
+    batch_cap(monkeypatch, 2)
+    cmd = ctx.drift_command()
+    st = ctx.simulate_stats()[1]
+    assert cmd == whole
+    assert (cmd["decision"], cmd["candidates"]) == (decision, cands)
+    assert decision != abi.KP_DRIFT_DELETE_EMPTY  # every candidate of these clusters holds pods: all are simulated
+    assert st[3] == NC and st[6] == _batches(NC, 2) and st[6] > 1
+    if decision == abi.KP_DRIFT_REPLACE:
+        assert cmd["n_nodeclaims"] == rows[cands[0]]["n_new_nodeclaims"] and cmd["row"] == refs[cands[0]]["row"]
+    else:
+        assert cmd["n_nodeclaims"] == 0 and cmd["row"] == dict.fromkeys(sim_ref.ROW_FIELDS, 0)
+
+
+# ------------------------------------------------------------------------------------------------
+# seven to twelve NodeClaims whose slice order decides
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(sim_ref.LADDERS))
+def test_slice_order_at_seven_to_twelve(ctx, cat, name):
+    """sim_ref.ladder_case: every floater joins the first NodeClaim of the re-sorted slice that lists its type
+    (tests/test_simulate_cpu.py::test_ladder_cases shows that a tie broken by id or a scan in id order goes elsewhere)."""
+    counts = sim_ref.LADDERS[name]
+    cp, _, floaters = sim_ref.ladder_case(cat, counts)
+    prepare(ctx, cp)
+    ref = cached_ref(("ladder", name), cp, SINGLE, 0)
+    n = len(counts)
+    pos = np.asarray(ref["results"].nodeclaim_slice_pos[:n]).tolist()
+    assert ref["n_nodeclaims"] == n and sorted(pos) == list(range(n)) and pos != list(range(n))
+    row = ctx.simulate_execute(SINGLE, 1)[0]
+    assert (row["status"], row["all_scheduled"], row["n_new_nodeclaims"], row["n_pods"]) == \
+        (abi.KP_SIM_OK, 1, n, sum(counts) + len(floaters))
+    check_probe(ctx, cp, SINGLE, 0, ref)
+    _, _, res, _ = ctx.simulate_nodeclaims(SINGLE, 0)
+    assert res.nodeclaim_slice_pos.tolist() == pos
+    for p, _ in floaters:
+        assert int(res.pod_result[p]) == int(ref["results"].pod_result[p])
+
+
+# ------------------------------------------------------------------------------------------------
+# the queue bitmap past 4096 pods
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", sim_ref.BITMAP_SEEDS)
+def test_queue_bitmap_second_block(ctx, cat, seed):
+    """sim_ref.bitmap_block_case: 4300 pods, so the queue bitmap has 68 words and the kernel's scan takes a second step;
+    the probes' pods sit at queue ranks on both sides of 4096 and of the word edges around it.  kp_consolidate_prepare
+    takes the cluster as it is, with most of its pods owned by no candidate and not pending: no extra candidate and no
+    sub-range was needed."""
+    cp, rank = sim_ref.bitmap_block_case(cat, seed)
+    assert cp.cluster.pods.n > 4096 + 64
+    prepare(ctx, cp)
+    for mode in (SINGLE, MULTI):
+        refs = cached_refs(("bitmap", seed), cp, mode)
+        sim_ref.assert_rows_equal(ctx.simulate_execute(mode, len(refs)), sim_ref.rows(cp, mode, refs))
+        for i, ref in enumerate(refs):
+            assert ref["row"]["status"] == abi.KP_SIM_OK
+            check_probe(ctx, cp, mode, i, ref)  # the row, the pods list, the Results and the requirements
+            _, pods, _, _ = ctx.simulate_nodeclaims(mode, i)
+            assert pods.tolist() == ref["pods"]
+            if mode == MULTI:
+                ranks = rank[pods[len(cp.pending):]]
+                assert ranks.min() < 4096 <= ranks.max()
