@@ -353,6 +353,8 @@ typedef struct kp_device_opts {
     int32_t preference_policy;               /* KP_PREFERENCE_*: Respect relaxes preferences (ScheduleAnyway spreads,
                                                 preferred affinities); Ignore drops them before scheduling */
     int32_t reserved_capacity;               /* feature gate ReservedCapacity: reserved offerings join Solve */
+    int32_t simulate_topology;               /* feature gate: 0 refuses passes with topology terms in the simulate, drift
+                                                and validate calls (KP_E_UNSUPPORTED); 1 simulates them */
 } kp_device_opts;
 
 typedef struct kp_ctx kp_ctx;
@@ -945,7 +947,10 @@ kp_status kp_consolidate_explain_stats(kp_ctx* ctx, double* ms, int64_t* counter
  * primary device of a multi-device ctx, and write nothing the pass keeps: kp_consolidate_execute, _command and _stats
  * return what they would have returned.
  *
- * Refused, never approximated.  Pass-wide, KP_E_UNSUPPORTED with a message: a cluster with topology terms; a catalog
+ * Refused, never approximated.  Pass-wide, KP_E_UNSUPPORTED with a message: a cluster with topology terms, unless the
+ * ctx was created with kp_device_opts.simulate_topology = 1 (then each probe keeps its own topology counts, as the
+ * consolidation probes do, with a hostname domain per new NodeClaim, and the NodeClaims' requirements carry the
+ * topology-narrowed keys); a catalog
  * with reserved offerings (the kernel runs the evaluation without reserved-offering rows; with the ReservedCapacity
  * gate on, the oracle's only entry point that runs the fallback reservation mode does not return NodeClaims past the
  * second, so nothing could check it); pod classes with preferences that can relax.  Per probe, KP_SIM_UNSUPPORTED_PROBE:

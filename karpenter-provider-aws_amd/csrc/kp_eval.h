@@ -107,7 +107,7 @@ struct ProbeTopo {
     int32_t* cnt;          // [G][64] value-keyed counts (row g valid when touched bit g is set)
     uint64_t* known;       // [G] registered domains of row g
     uint64_t* touched;     // LDS [ceil(G / 64)]
-    int32_t* hd;           // [HG][E + 1] hostname-count deltas
+    int32_t* hd;           // [HG][E + 1] hostname-count deltas ([HG][E + KP_PT_SIM_COLS] in a simulate probe)
     uint64_t* hmod;        // LDS [EW]: node column valid
     const uint64_t* dgk;   // [G] domains of buildDomainGroups (registered before any pod is counted)
     int32_t* hpos;         // LDS [n_ha]: hostname domains holding a selected pod, per hostname-affinity group
@@ -147,7 +147,7 @@ struct EvalEnv {
     const uint32_t* type_ro;   // [T] the type's reserved-offering rows (packed, ro_span_bits)
     const int32_t* rcap;       // ReservationManager capacity by reservation (ResvTab::rid; LDS)
     int resv_on;               // run the reservation step of NodeClaim.Add
-    const ProbeTopo* pt;       // consolidation probe topology counts (eval_wave<..., CT = true>)
+    const ProbeTopo* pt;       // probe topology counts (eval_wave<..., CT != 0>)
     const TopoSnap* snap;      // FFD kernel: the current pod's topology snapshot (null: read the global counters)
 };
 
@@ -432,7 +432,8 @@ __device__ __forceinline__ int wave_min_i32(int x) {
 // ---- probe topology counts (ProbeTopo) ----
 // Row g of the probe's value-keyed counts: base - dec (the probe's candidates' pods, at probe start) or the base (first
 // use); its registered domains are buildDomainGroups' plus every domain with a positive count.  Hostname rows: column
-// j < E is node j, column E the probe's in-flight NodeClaim, E + 1 a NodeClaim being created (no pods yet).
+// j < E is node j, column E the probe's in-flight NodeClaim, E + 1 a NodeClaim being created (no pods yet); a simulate
+// probe has a column per NodeClaim id (pt_hcnt).
 __device__ inline void pt_init_row(const KpDev& d, const ProbeTopo& P, int g, const int32_t* dec, int lane) {
     const int32_t v = d.tg_cnt[(size_t)g * 64 + lane] - (dec ? dec[lane] : 0);
     __hip_atomic_store(&P.cnt[(size_t)g * 64 + lane], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -447,10 +448,20 @@ __device__ __forceinline__ void pt_row(const KpDev& d, const ProbeTopo& P, int g
     const uint64_t t = __builtin_amdgcn_readfirstlane((int)(uint32_t)(P.touched[g >> 6] >> (g & 63))) & 1;
     if (!t) pt_init_row(d, P, g, nullptr, lane);
 }
+// NC: the NodeClaim columns of a hostname row.  One for a consolidation probe; KP_PT_SIM_COLS for a simulate probe, whose
+// NodeClaim `id` counts in column E + id (a host past the last column is a NodeClaim that cannot exist yet: empty).
+#define KP_PT_SIM_COLS 12
+constexpr int pt_cols(int CT) { return CT == 2 ? KP_PT_SIM_COLS : 1; }
+template <int NC = 1>
 __device__ __forceinline__ int pt_hcnt(const KpDev& d, const ProbeTopo& P, int hrow, int host) {
-    int32_t* col = P.hd + (size_t)hrow * (P.E + 1);
-    if (host > P.E) return 0;  // a NodeClaim not created yet
-    if (host == P.E) return ld_i32(col + P.E);
+    int32_t* col = P.hd + (size_t)hrow * (P.E + NC);
+    if constexpr (NC == 1) {
+        if (host > P.E) return 0;  // a NodeClaim not created yet
+        if (host == P.E) return ld_i32(col + P.E);
+    } else {
+        if (host >= P.E + NC) return 0;
+        if (host >= P.E) return ld_i32(col + host);
+    }
     int c = d.tg_hcnt[(size_t)hrow * d.HN + host];
     if ((P.hmod[host >> 6] >> (host & 63)) & 1ull) c += ld_i32(col + host);
     return c;
@@ -459,7 +470,7 @@ __device__ __forceinline__ int pt_hcnt(const KpDev& d, const ProbeTopo& P, int h
 // the pod's domains admit holds a selected pod (options.Len() == 0).  podDomains is every host unless the pod requires
 // the hostname (T.hdom): In — none of the listed existing nodes is positive; NotIn — every positive host is listed.
 // A listed node among a consolidation probe's candidates counts what its own reschedulable pods leave.  Whole wave.
-template <bool CT>
+template <int CT>
 __device__ inline bool host_aff_unseeded(const KpDev& d, const KpTopoCons& T, int g, const ProbeTopo* pt, int lane) {
     const int pos = CT ? pt->hpos[pt->ha[g]] : ld_i32(&d.tg_pos[g]);
     const int mode = T.hdom & 3;
@@ -471,7 +482,7 @@ __device__ inline bool host_aff_unseeded(const KpDev& d, const KpTopoCons& T, in
         if (b + lane < n) {
             const int2 h = d.tce_hosts[T.podhas + b + lane];
             if (CT && ((pt->excl[h.x >> 6] >> (h.x & 63)) & 1ull)) p = h.y != 0;
-            else p = (CT ? pt_hcnt(d, *pt, hrow, h.x) : ld_i32(&d.tg_hcnt[(size_t)hrow * d.HN + h.x])) > 0;
+            else p = (CT ? pt_hcnt<pt_cols(CT)>(d, *pt, hrow, h.x) : ld_i32(&d.tg_hcnt[(size_t)hrow * d.HN + h.x])) > 0;
         }
         np += __popcll(ballot(p));
     }
@@ -479,14 +490,15 @@ __device__ inline bool host_aff_unseeded(const KpDev& d, const KpTopoCons& T, in
 }
 
 // one more pod counted in hostname row hrow at `host` (whole wave)
+template <int NC = 1>
 __device__ inline void pt_hadd(const ProbeTopo& P, int hrow, int host, int lane) {
     if (host < P.E && !((P.hmod[host >> 6] >> (host & 63)) & 1ull)) {
         for (int r = lane; r < P.HG; r += 64)
-            __hip_atomic_store(&P.hd[(size_t)r * (P.E + 1) + host], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&P.hd[(size_t)r * (P.E + NC) + host], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) P.hmod[host >> 6] |= 1ull << (host & 63);
     }
-    if (lane == 0) atomicAdd(&P.hd[(size_t)hrow * (P.E + 1) + host], 1);
+    if (lane == 0) atomicAdd(&P.hd[(size_t)hrow * (P.E + NC) + host], 1);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 }
 
@@ -498,8 +510,9 @@ __device__ inline void pt_hadd(const ProbeTopo& P, int hrow, int host, int lane)
 // iteration order; the smallest value name (vrank) is the canonical choice (oracle/orc_solve.cpp topo_get).
 // Hostname groups: the candidate's own host is the only domain its requirements allow (hostname In [host]).
 // ws.memo_ok is cleared when the outcome depends on counts (a count check failed or a key was narrowed).
-// CT: the counts are a consolidation probe's (pt).
-template <bool CT = false>
+// CT: the counts are a probe's (pt): 1 a consolidation probe's (one NodeClaim column), 2 a simulate probe's
+// (KP_PT_SIM_COLS NodeClaim columns).
+template <int CT = 0>
 __device__ __forceinline__ bool topo_narrow(const KpDev& d, const ClassCache& CC, WaveScratch& ws, int host, bool allow_wk,
                                          int lane, const ProbeTopo* pt = nullptr, const TopoSnap* snap = nullptr) {
     int nk = 0;
@@ -519,7 +532,7 @@ __device__ __forceinline__ bool topo_narrow(const KpDev& d, const ClassCache& CC
         }
         const int type = info.x & TG_TYPE;
         if (info.x & TG_HOST) {
-            const int cnt = CT ? pt_hcnt(d, *pt, d.tg_hrow[g], host) : ld_i32(&d.tg_hcnt[(size_t)d.tg_hrow[g] * d.HN + host]);
+            const int cnt = CT ? pt_hcnt<pt_cols(CT)>(d, *pt, d.tg_hrow[g], host) : ld_i32(&d.tg_hcnt[(size_t)d.tg_hrow[g] * d.HN + host]);
             bool ok;
             if (type == 0) ok = cnt + self <= info.z;             // spread: hostname domainMinCount is 0
             else if (type == 2) ok = cnt == 0;                    // anti-affinity: an empty domain
@@ -665,7 +678,7 @@ __device__ inline bool topo_filter_compatible(const KpDev& d, const ClassCache& 
 
 // exnode >= 0: the placement is on existing node exnode (its taints: ex_tol; its hostname is a real node name).
 // born: the late identities created so far (the FFD kernel's; a probe's is *pt->born).
-template <bool CT = false>
+template <int CT = 0>
 __device__ __forceinline__ void topo_record(const KpDev& d, const ClassCache& CC, const WaveScratch& ws, const ReqHdr* Ahdr,
                                          const uint64_t* Aw, int host, int tmpl, bool allow_wk, int lane, int exnode = -1,
                                          const ProbeTopo* pt = nullptr, uint64_t born = ~0ull) {
@@ -704,9 +717,9 @@ __device__ __forceinline__ void topo_record(const KpDev& d, const ClassCache& CC
         if (info.x & TG_HOST) {
             if (CT) {
                 // a hostname-affinity group's domain becomes positive: one more domain holds a selected pod
-                if (!inv && type == 1 && pt->ha[g] >= 0 && pt_hcnt(d, *pt, d.tg_hrow[g], host) == 0 && lane == 0)
+                if (!inv && type == 1 && pt->ha[g] >= 0 && pt_hcnt<pt_cols(CT)>(d, *pt, d.tg_hrow[g], host) == 0 && lane == 0)
                     pt->hpos[pt->ha[g]]++;
-                pt_hadd(*pt, d.tg_hrow[g], host, lane);
+                pt_hadd<pt_cols(CT)>(*pt, d.tg_hrow[g], host, lane);
             } else if (lane == 0) {
                 const int old = atomicAdd(&d.tg_hcnt[(size_t)d.tg_hrow[g] * d.HN + host], 1);
                 if (old == 0) atomicAdd(&d.tg_pos[g], 1);
@@ -731,7 +744,7 @@ __device__ __forceinline__ void topo_record(const KpDev& d, const ClassCache& CC
 // the node's requirements (no undefined-label allowance), then Topology.AddRequirements with the node's own domains
 // (hostname = the node's name: host row j).  On success ws holds the merged class keys.  nh_in / nw_in: the node's
 // requirements digest when it is not d.ex_hdr's row j (a consolidation probe's copy of a node it changed).
-template <bool CONS, bool CT = false>
+template <bool CONS, int CT = 0>
 __device__ inline bool existing_topo_try(const KpDev& d, const ClassCache& CC, WaveScratch& ws, int j, int lane,
                                          const ProbeTopo* pt = nullptr, const ReqHdr* nh_in = nullptr,
                                          const uint64_t* nw_in = nullptr) {
@@ -811,7 +824,7 @@ __device__ inline void existing_topo_commit(const KpDev& d, const ClassCache& CC
 // the requirement, topology and offering steps run in each wave alike, the type sweep is split over the waves by word,
 // and one block barrier joins the partial sweeps; every wave ends with the same result in its ws.
 // PROF: the diagnostic twins of the Solve kernels (ffd_solve PROF): stage stamps into a.prof under KPSIM_PROFILE.
-template <bool TOPO, bool RESV = false, bool STRICT = true, bool BE = true, bool CT = false, bool TEAM = false,
+template <bool TOPO, bool RESV = false, bool STRICT = true, bool BE = true, int CT = 0, bool TEAM = false,
           bool PROF = false>
 __device__ __forceinline__ bool eval_wave(const KpDev& d, const EvalEnv& E, const ClassCache& CC, const EvalIn& a,
                                           WaveScratch& ws, int lane, TeamBuf* tb = nullptr, int trank = 0, int tn = 1,

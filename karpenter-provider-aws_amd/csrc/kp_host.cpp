@@ -378,6 +378,7 @@ struct kp_ctx {
     std::string err;
     int pref_policy = KP_PREFERENCE_RESPECT;  // kp_device_opts solver parameters
     int reserved_capacity = 1;
+    int simulate_topology = 0;  // kp_device_opts::simulate_topology
     // catalog (host copies)
     bool have_catalog = false;
     uint64_t epoch = 0;
@@ -640,6 +641,8 @@ struct kp_ctx {
     DBuf<int64_t> d_sm_req, d_sm_delta, d_sm_stats;
     DBuf<int32_t> d_sm_tmpl, d_sm_count, d_sm_npods, d_sm_spos, d_sm_nopts, d_sm_valid, d_sm_types, d_sm_ntypes,
         d_sm_nonpend, d_sm_log, d_sm_nlog, d_sm_err, d_sm_ring, d_sm_rlast, d_sm_ov_slot;
+    DBuf<int32_t> d_sm_pt_cnt, d_sm_pt_hd;  // simulate_topo_kernel's per-worker ProbeTopo
+    DBuf<uint64_t> d_sm_pt_known;
     DBuf<KpSimRow> d_sm_rows;
     DBuf<KpDev> d_sm_dev;
     DBuf<KpCons> d_sm_k;
@@ -731,6 +734,7 @@ extern "C" kp_status kp_ctx_create(const kp_device_opts* opts, kp_ctx** out) try
             return KP_E_INVALID;
         ctx->pref_policy = opts->preference_policy;
         ctx->reserved_capacity = opts->reserved_capacity ? 1 : 0;
+        ctx->simulate_topology = opts->simulate_topology ? 1 : 0;
     }
     if (ctx->device < 0 || ctx->device >= n) return KP_E_DEVICE;
     if (hipSetDevice(ctx->device) != hipSuccess) return KP_E_DEVICE;
@@ -5222,9 +5226,9 @@ static kp_status sim_check(kp_ctx* ctx, const char* who, int mode) {
     if (!cons_explainable(ctx))
         return fail(ctx, KP_E_STATE, std::string(who) + " needs a prepared pass (none since the last prepare, catalog "
                                                         "upload or availability patch)");
-    if (ctx->cons.G > 0)
-        return fail(ctx, KP_E_UNSUPPORTED, std::string(who) + ": the cluster has topology terms (the simulate kernel keeps no "
-                                                              "per-probe topology counts)");
+    if (ctx->cons.G > 0 && !ctx->simulate_topology)
+        return fail(ctx, KP_E_UNSUPPORTED, std::string(who) + ": the cluster has topology terms (simulated only with "
+                                                              "kp_device_opts.simulate_topology = 1)");
     if (ctx->dev.ro)
         return fail(ctx, KP_E_UNSUPPORTED, std::string(who) + ": the catalog has reserved offerings (the simulate kernel "
                                                               "evaluates NodeClaims without reserved-offering rows)");
@@ -5286,13 +5290,15 @@ static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* r
     k.mode = mode;
     k.ring_cap = std::max(1, c->cons_n_pending + maxp);
     KpSim x{};
-    if (!kp_sim_plan_lds(d, x, KP_LDS_BYTES)) return fail(ctx, KP_E_UNSUPPORTED, "simulate LDS plan exceeds 160 KB");
+    const size_t G = (size_t)std::max(k.G, 0), HG = (size_t)std::max(k.HG, 1);
+    if (!kp_sim_plan_lds(d, x, KP_LDS_BYTES, k.G, k.n_ha)) return fail(ctx, KP_E_UNSUPPORTED, "simulate LDS plan exceeds 160 KB");
     // batch size: the workers' slabs and scratch stay within about 64 MB
     // a MUT probe copies a node's digest when a merge first changes it: at most once per node and per pod it places
     x.ov_cap = k.mut ? (int)std::max<size_t>(1, std::min<size_t>(E, (size_t)k.ring_cap)) : 1;
     const size_t per = NCM * (K * sizeof(ReqHdr) + DW * 8 + TW * 8 + R * 8 + M * 4 + 40) + (size_t)k.ring_cap * 16 +
                        A * E * 8 + (size_t)k.PW * 8 +
-                       (k.mut ? E * 4 + (size_t)x.ov_cap * (K * sizeof(ReqHdr) + DW * 8) : 0);
+                       (k.mut ? E * 4 + (size_t)x.ov_cap * (K * sizeof(ReqHdr) + DW * 8) : 0) +
+                       (G ? G * 64 * 4 + G * 8 + HG * (E + NCM) * 4 : 0);  // a topology pass: the worker's ProbeTopo
     int W = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)64 << 20) / per)));
     if (const char* e = getenv("KPSIM_SIM_BATCH"))  // diagnostics: KPSIM_SIM_BATCH=n runs at most n probes per batch
         if (atoi(e) >= 1) W = std::min(W, atoi(e));
@@ -5332,6 +5338,28 @@ static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* r
     HIPCHK(c->d_sm_ov_slot.ensure(k.mut ? (size_t)W * E : 1));
     HIPCHK(c->d_sm_ov_hdr.ensure((size_t)W * x.ov_cap * K));
     HIPCHK(c->d_sm_ov_words.ensure((size_t)W * x.ov_cap * DW));
+    if (G) {
+        // per-worker probe topology counts (ProbeTopo), the simulate call's own: the pass's d_pt_* stay untouched.  The
+        // base counts, the probes' decrements and the hostname-affinity tables of the prepared pass are read-only here
+        HIPCHK(c->d_sm_pt_cnt.ensure((size_t)W * G * 64));
+        HIPCHK(c->d_sm_pt_known.ensure((size_t)W * G));
+        HIPCHK(c->d_sm_pt_hd.ensure((size_t)W * HG * (E + NCM)));
+        x.pt_cnt = c->d_sm_pt_cnt.p;
+        x.pt_known = c->d_sm_pt_known.p;
+        x.pt_hd = c->d_sm_pt_hd.p;
+        k.pt_cnt = nullptr;
+        k.pt_known = nullptr;
+        k.pt_hd = nullptr;
+        k.pt_dgk = c->d_pt_dgk.p;
+        k.dec_soff = c->d_dec_soff.p;
+        k.dec_moff = c->d_dec_moff.p;
+        k.dec_g = c->d_dec_g.p;
+        k.dec_v = c->d_dec_v.p;
+        k.tg_ha = c->d_tg_ha.p;
+        k.hpos0 = c->d_hpos0.p;
+        d.tg_cnt = c->d_tg_cnt0.p;
+        d.tg_hcnt = c->d_tg_hcnt0.p;
+    }
     HIPCHK(c->d_sm_dev.ensure(1));
     HIPCHK(c->d_sm_k.ensure(1));
     HIPCHK(c->d_sm_x.ensure(1));
@@ -5399,13 +5427,14 @@ static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* r
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, c->smev[0], c->smev[1]));
         c->sm_ms[0] += ms;
-        if (err) return fail(ctx, KP_E_DEVICE, "simulate_kernel: a probe exceeded its pop bound (internal error)");
+        const std::string kname = k.G > 0 ? "simulate_topo_kernel" : "simulate_kernel";  // the entry that ran
+        if (err) return fail(ctx, KP_E_DEVICE, kname + ": a probe exceeded its pop bound (internal error)");
         // the slabs are NodeClaim-major over the batch: finalize_kernel runs over the entries of the NodeClaims the batch
         // created (most NodeClaims of any probe x workers) and leaves the rest alone
         int most = 0;
         for (int i = 0; i < nb; i++) {
             if (dr[i].status == KP_SIM_OK && (dr[i].n_nc < 0 || dr[i].n_nc > (int)NCM))
-                return fail(ctx, KP_E_DEVICE, "simulate_kernel: inconsistent row");
+                return fail(ctx, KP_E_DEVICE, kname + ": inconsistent row");
             if (dr[i].status == KP_SIM_OK) most = std::max(most, dr[i].n_nc);
         }
         const int32_t used = most * nb;
@@ -5451,7 +5480,7 @@ static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* r
             t.npods.resize(N), t.spos.resize(N), t.nopts.resize(N), t.valid.resize(N), t.ntypes.resize(N), t.tmpl.resize(N);
             t.types.resize((size_t)N * M), t.h.resize((size_t)N * K), t.w.resize((size_t)N * DW);
             HIPCHK(hipMemcpy(&t.n_log, c->d_sm_nlog.p, 4, hipMemcpyDeviceToHost));
-            if (t.n_log < 0 || t.n_log > k.ring_cap) return fail(ctx, KP_E_DEVICE, "simulate_kernel: inconsistent placement log");
+            if (t.n_log < 0 || t.n_log > k.ring_cap) return fail(ctx, KP_E_DEVICE, kname + ": inconsistent placement log");
             t.log.resize((size_t)t.n_log * 2);
             if (t.n_log) HIPCHK(hipMemcpy(t.log.data(), c->d_sm_log.p, (size_t)t.n_log * 8, hipMemcpyDeviceToHost));
             if (N > 0) {
@@ -5467,7 +5496,7 @@ static kp_status sim_run(kp_ctx* ctx, int mode, int b0, int b1, kp_sim_result* r
             }
             for (int q = 0; q < N; q++)
                 if (t.tmpl[q] < 0 || t.tmpl[q] >= (int)c->tmpl_np.size() || t.ntypes[q] < 0 || t.ntypes[q] > (int)M)
-                    return fail(ctx, KP_E_DEVICE, "simulate_kernel: inconsistent NodeClaim record");
+                    return fail(ctx, KP_E_DEVICE, kname + ": inconsistent NodeClaim record");
         }
     }
     int64_t st[SS_COUNT];

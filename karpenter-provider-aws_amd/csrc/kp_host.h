@@ -33,6 +33,6 @@ hipError_t kp_launch_cons_prep(const int32_t* queue0, int P, int32_t* rank, cons
                                uint64_t* pend_bits, hipStream_t s);
 hipError_t kp_queue_sort(const int64_t* fields, int n, int32_t* perm_a, int32_t* perm_b, uint64_t* keys_a,
                          uint64_t* keys_b, void* temp, size_t* temp_bytes, hipStream_t s, int32_t** result);
-bool kp_sim_plan_lds(const KpDev& d, KpSim& x, int max_bytes);
+bool kp_sim_plan_lds(const KpDev& d, KpSim& x, int max_bytes, int G = 0, int n_ha = 0);
 hipError_t kp_launch_simulate(const KpCons& k, const KpSim& x, hipStream_t s, const KpDev* d_dev, const KpCons* d_k,
                               const KpSim* d_x);

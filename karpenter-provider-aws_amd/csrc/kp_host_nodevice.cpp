@@ -29,7 +29,7 @@ hipError_t kp_launch_consolidate_explain(const KpDev& d, const KpCons& k, const 
 // kp_simulate.hip's launchers: nothing is simulated, every probe reports an empty queue with everything scheduled and no
 // NodeClaim, except that in a pass with host ports or volume limits its MUT probes count as the probes the kernel does
 // not cover (the host layer's batching, row folding and decoding still run end to end).
-bool kp_sim_plan_lds(const KpDev&, KpSim& x, int) {
+bool kp_sim_plan_lds(const KpDev&, KpSim& x, int, int, int) {
     x.lds_bytes = 1024;
     return true;
 }

@@ -39,4 +39,11 @@ struct KpSim {
     // dynamic LDS plan (kp_sim_plan_lds)
     int32_t off_hdr, off_words, off_rem, off_excl, off_mod, off_mutn;
     int32_t lds_bytes;
+    // simulate_topo_kernel (a pass with topology groups, kp_device_opts::simulate_topology): each worker's ProbeTopo
+    // (kp_eval.h), as consolidate_body's but with a hostname column per NodeClaim id.  The prepared pass's own pt_*
+    // buffers are not used; its base counts, decrements and hostname-affinity tables are read through KpDev / KpCons.
+    int32_t* pt_cnt;       // [workers][G][64]
+    uint64_t* pt_known;    // [workers][G]
+    int32_t* pt_hd;        // [workers][HG][E + KP_SIM_MAX_NODECLAIMS]
+    int32_t off_touch, off_hmod, off_hpos, off_born;  // LDS: touched rows [ceil(G / 64)], node columns [EW], hpos [n_ha], born
 };

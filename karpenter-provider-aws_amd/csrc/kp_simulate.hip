@@ -21,7 +21,14 @@
 // in the worker's ov_* slab, the changed nodes in an LDS bitmap, and class x node compatibility of such a node evaluated
 // against its copy.
 //
-// Not covered (the host refuses, kp_simulate_execute): topology groups, reserved offerings, preference relaxation; and per
+// TOPO (simulate_topo_kernel; a pass with topology groups, behind kp_device_opts::simulate_topology): as
+// consolidate_body's TOPO instantiation, each probe keeps its own domain counts (ProbeTopo, kp_eval.h: the prepared base
+// minus the pods it reschedules), with one hostname column per NodeClaim id (E + id) where consolidate_body has one for
+// its only NodeClaim.  A pod of a constrained class (CF_TOPO_CONS) runs Topology.AddRequirements on every fitting node
+// in order, on each in-flight NodeClaim and on the templates (host E + n_nc: no pod counted there); every placement of
+// a counted class (CF_TOPO) is recorded.
+//
+// Not covered (the host refuses, kp_simulate_execute): reserved offerings, preference relaxation; and per
 // probe (KP_SIM_UNSUPPORTED_PROBE): a probe that reschedules a pod with host ports or with claims on a limited CSI driver
 // (their per-probe overlays are not modelled here).
 #include <hip/hip_runtime.h>
@@ -78,14 +85,14 @@ __device__ inline uint64_t sim_limit_filter(const KpDev& d, int j, uint64_t o, c
 
 }  // namespace
 
+static_assert(KP_PT_SIM_COLS == KP_SIM_MAX_NODECLAIMS, "a hostname column per NodeClaim id");
+
 // d / k / x: device copies of the launch's tables, read through const references (a by-value KpDev indexed dynamically
 // goes to scratch per lane, see kp_consolidate.hip).  Block b runs probe k.probe0 + b of k.mode (SINGLE or MULTI) as
 // worker b: one probe per worker, so the batch's slabs hold every probe's NodeClaims when the kernel ends.
-__global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ dp, const KpCons* __restrict__ kp,
-                                                      const KpSim* __restrict__ xp) {
-    const KpDev& d = *dp;
-    const KpCons& k = *kp;
-    const KpSim& x = *xp;
+template <bool TOPO>
+__device__ __forceinline__ void simulate_body(const KpDev& d, const KpCons& k, const KpSim& x) {
+    constexpr int CT = 2;  // kp_eval.h: a simulate probe's ProbeTopo
     extern __shared__ __attribute__((aligned(16))) char smem[];
     SimShared& S = *reinterpret_cast<SimShared*>(smem);
     ReqHdr* nch = reinterpret_cast<ReqHdr*>(smem + x.off_hdr);
@@ -101,6 +108,21 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
     const int32_t* const pshape = d.pod_shape0 ? d.pod_shape0 : d.pod_shape;
     const int E = d.E, EW = d.EW, A = d.n_active, R = d.R, K = d.K, DW = d.DW, TW = d.TW, T = d.T, NT = d.NT;
     const int cap = k.ring_cap;
+    ProbeTopo P{};
+    if constexpr (TOPO) {
+        P.cnt = x.pt_cnt + (size_t)wid * k.G * 64;
+        P.known = x.pt_known + (size_t)wid * k.G;
+        P.touched = reinterpret_cast<uint64_t*>(smem + x.off_touch);
+        P.hd = x.pt_hd + (size_t)wid * (k.HG > 0 ? k.HG : 1) * (E + KP_PT_SIM_COLS);
+        P.hmod = reinterpret_cast<uint64_t*>(smem + x.off_hmod);
+        P.dgk = k.pt_dgk;
+        P.hpos = reinterpret_cast<int32_t*>(smem + x.off_hpos);
+        P.ha = k.tg_ha;
+        P.born = reinterpret_cast<uint64_t*>(smem + x.off_born);
+        P.excl = excl;
+        P.E = E;
+        P.HG = k.HG;
+    }
     int32_t* ring = k.ring + (size_t)wid * cap;
     int32_t* rlast = k.ring_last + (size_t)wid * cap;
     int64_t* delta = k.delta + (size_t)wid * (A > 0 ? A : 1) * (E > 0 ? E : 1);
@@ -169,7 +191,7 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
     Ev.type_ro = nullptr;
     Ev.rcap = nullptr;
     Ev.resv_on = 0;
-    Ev.pt = nullptr;
+    Ev.pt = TOPO ? &P : nullptr;
     Ev.snap = nullptr;
 
     // ---- probe state: excluded candidates, NodePool limits + the candidates' capacity ----
@@ -183,6 +205,28 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
                     atomicAdd((unsigned long long*)&rem[tj * R + r], (unsigned long long)k.cand_cap[(size_t)c * R + r]);
     }
     __syncthreads();
+    if constexpr (TOPO) {
+        // this probe's NewTopology: no row copied yet, no node column of its own, every NodeClaim column empty; then the
+        // pods it reschedules come off the base counts
+        for (int w = lane; w < ((k.G + 63) >> 6); w += 64) P.touched[w] = 0;
+        for (int w = lane; w < EW; w += 64) P.hmod[w] = 0;
+        for (int i = lane; i < k.HG * KP_PT_SIM_COLS; i += 64)
+            __hip_atomic_store(&P.hd[(size_t)(i / KP_PT_SIM_COLS) * (E + KP_PT_SIM_COLS) + E + i % KP_PT_SIM_COLS], 0,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const int r0 = single ? k.dec_soff[gp] : k.dec_moff[gp], r1 = single ? k.dec_soff[gp + 1] : k.dec_moff[gp + 1];
+        for (int r = r0; r < r1; r++) {
+            const int g = k.dec_g[r];
+            if (g >= 0 && g < k.G) pt_init_row(d, P, g, k.dec_v + (size_t)r * 64, lane);
+        }
+        for (int ga = lane; ga < k.n_ha; ga += 64) P.hpos[ga] = k.hpos0[(size_t)(single ? gp : k.n_cand + gp) * k.n_ha + ga];
+        if (lane == 0) {
+            *P.born = k.born_s ? (single ? k.born_s[gp] : k.born_m[gp]) : ~0ull;
+            if (d.late_sib) S.CC.cls = -1;  // the class caches route variant groups by this probe's births
+        }
+        sim_sync_mem();
+        __syncthreads();
+    }
 
     // ---- the probe's pods in queue order: mark queue positions, then scan the bitmap with the pending pods ----
     const int po0 = k.cand_off[c0], po1 = k.cand_off[c1];
@@ -326,13 +370,33 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             prev_shape = shape;
             xstart = 0;
         }
+        // TOPO: a class counted by some group records each placement; a constrained class's node rejections depend on
+        // counts (scan from the first node, no resume)
+        uint32_t cflags = 0;
+        if constexpr (TOPO) {
+            cflags = __builtin_amdgcn_readfirstlane(d.cls_flags[c]);
+            if ((cflags & CF_TOPO) && S.CC.cls != c) fill_class_cache<true>(d, c, S.CC, lane, 64, *P.born);
+        }
+        const bool ctopo = TOPO && (cflags & CF_TOPO);
+        const bool tcons = TOPO && (cflags & CF_TOPO_CONS);
+        const int xs = tcons ? 0 : xstart;
+        // MUT: the requirements digest of node j as this probe sees it (its copy once a merge changed it)
+        auto node_digest = [&](int j, const ReqHdr*& h, const uint64_t*& w) {
+            h = d.ex_hdr + (size_t)j * K;
+            w = d.ex_words + (size_t)j * DW;
+            if (mutp && ((mutn[j >> 6] >> (j & 63)) & 1ull)) {
+                const int sl = __builtin_amdgcn_readfirstlane(sld32(&ov_slot[j]));
+                h = ov_hdr + (size_t)sl * K;
+                w = ov_words + (size_t)sl * DW;
+            }
+        };
 
         // ---- 1. ExistingNode.Add: first fit in scheduling order, 64 nodes per ballot ----
         int jf = -1;
-        for (int base = xstart & ~63; base < E; base += 64) {
+        for (int base = xs & ~63; base < E; base += 64) {
             const int w = base >> 6;
             const int j = base + lane;
-            const uint64_t ge = xstart > base ? (~0ull << (xstart - base)) : ~0ull;
+            const uint64_t ge = xs > base ? (~0ull << (xs - base)) : ~0ull;
             uint64_t xw = d.XT[(size_t)c * EW + w] & ~excl[w];
             if (mutp) {
                 // the nodes this probe changed, re-evaluated against their copies: taints tolerated, static fit,
@@ -360,7 +424,19 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
                     cand = preq[d.active_axes[ai]] <= h;
                 }
             }
-            const uint64_t m = ballot(cand);
+            uint64_t m = ballot(cand);
+            if constexpr (TOPO) {
+                if (tcons) {  // ExistingNode.Add's topology step on each fitting node, in order (at most 64 per word)
+                    while (m) {
+                        const int jj = __builtin_amdgcn_readfirstlane(base + __ffsll((unsigned long long)m) - 1);
+                        const ReqHdr* nh;
+                        const uint64_t* nwd;
+                        node_digest(jj, nh, nwd);
+                        if (existing_topo_try<true, CT>(d, S.CC, S.ws, jj, lane, &P, nh, nwd)) break;
+                        m &= m - 1;
+                    }
+                }
+            }
             if (m) {
                 jf = base + __ffsll((unsigned long long)m) - 1;
                 break;
@@ -379,6 +455,15 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             if (lane == 0) modb[jf >> 6] |= 1ull << (jf & 63);
             sim_sync_mem();
             __syncthreads();
+            if constexpr (TOPO) {
+                if (ctopo) {  // Topology.Record with the node's merged requirements and taints
+                    const ReqHdr* nh;
+                    const uint64_t* nwd;
+                    node_digest(jf, nh, nwd);
+                    if (!tcons) existing_topo_try<false, CT>(d, S.CC, S.ws, jf, lane, &P, nh, nwd);
+                    topo_record<CT>(d, S.CC, S.ws, nh, nwd, jf, -1, false, lane, jf, &P);
+                }
+            }
             if (mutp) {
                 // ExistingNode.Add: nodeRequirements.Add(pod requirements).  A node's labels are single values that a
                 // compatible merge keeps, so only a class key the node lacks can change it: the first such merge copies
@@ -410,17 +495,25 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
                 if (sl >= 0) {
                     ReqHdr* nh = ov_hdr + (size_t)sl * K;
                     uint64_t* nwd = ov_words + (size_t)sl * DW;
-                    for (int i = d.cls_xkoff[c] + lane; i < d.cls_xkoff[c + 1]; i += 64) {
-                        const int kk = d.cls_xkeys[i];
-                        ReqHdr a = nh[kk];
-                        req_merge_inplace(d, kk, a, nwd + d.woff[kk], d.cls_hdr[(size_t)c * K + kk],
-                                          d.cls_words + (size_t)c * DW + d.woff[kk]);
-                        nh[kk] = a;
+                    if (ctopo) {  // ... then .Add(topology requirements): ws holds the merged class keys
+                        if (lane < S.CC.nck) {
+                            const int kk = S.CC.key[lane];
+                            nh[kk] = S.ws.hdr[lane];
+                            for (int i = 0; i < S.CC.nw[lane]; i++) nwd[S.CC.woff[lane] + i] = S.ws.words[S.CC.wsoff[lane] + i];
+                        }
+                    } else {
+                        for (int i = d.cls_xkoff[c] + lane; i < d.cls_xkoff[c + 1]; i += 64) {
+                            const int kk = d.cls_xkeys[i];
+                            ReqHdr a = nh[kk];
+                            req_merge_inplace(d, kk, a, nwd + d.woff[kk], d.cls_hdr[(size_t)c * K + kk],
+                                              d.cls_words + (size_t)c * DW + d.woff[kk]);
+                            nh[kk] = a;
+                        }
                     }
                     sim_sync_mem();
                 }
             }
-            xstart = jf;
+            if (!tcons) xstart = jf;
             if (!pend) {
                 // SimulateScheduling: a non-pending pod on an uninitialized node is an error
                 // (the pod has a place all the same: it is not among the unscheduled)
@@ -430,7 +523,7 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             log_place(p, -2 - jf);
             continue;
         }
-        xstart = E;
+        if (!tcons) xstart = E;
 
         // ---- 2. the in-flight NodeClaims in sort.Slice(newNodeClaims, len(Pods)) order ----
         // at most 12 elements: Go's pdqsort_func is insertionSort, a stable sort of the slice as the last sort left it
@@ -460,7 +553,7 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             const int tj = __builtin_amdgcn_readfirstlane(__shfl(id_tmpl, id));
             const int lc = __builtin_amdgcn_readfirstlane(__shfl(id_lc, id));
             if (staged != id) stage(id);
-            if (S.CC.cls != c) fill_class_cache<false>(d, c, S.CC, lane, 64, 0ull);
+            if (S.CC.cls != c) fill_class_cache<TOPO>(d, c, S.CC, lane, 64, TOPO ? *P.born : 0ull);
             EvalIn a;
             a.Ahdr = nch;
             a.Aw = ncw;
@@ -471,17 +564,22 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             a.compat = true;
             a.force_off = false;
             a.prof = nullptr;
-            a.host = E;
+            a.host = TOPO ? E + id : E;  // the NodeClaim's hostname column
             a.held = 0;
             st_nc++;
-            // the NodeClaim has absorbed the class, or the class's requirement merge changes nothing: Fits (+ minValues)
-            bool absorbed = c == lc;
-            if (!absorbed && ((d.tol[c] >> tj) & 1ull) && merge_noop_at(d, S.ws, nch, ncw, c, lane)) absorbed = true;
+            // the NodeClaim has absorbed the class, or the class's requirement merge changes nothing: Fits (+ minValues);
+            // never for a class some topology group counts or constrains
+            bool absorbed = c == lc && !ctopo;
+            if (!absorbed && !ctopo && ((d.tol[c] >> tj) & 1ull) && merge_noop_at(d, S.ws, nch, ncw, c, lane)) absorbed = true;
             bool ok;
             if (absorbed) {
                 ok = eval_fits_only<true>(d, Ev, a, S.ws, lane);
             } else {
-                ok = eval_wave<false, false, false>(d, Ev, S.CC, a, S.ws, lane);
+                if constexpr (TOPO)
+                    ok = tcons ? eval_wave<true, false, false, true, CT>(d, Ev, S.CC, a, S.ws, lane)
+                               : eval_wave<false, false, false>(d, Ev, S.CC, a, S.ws, lane);
+                else
+                    ok = eval_wave<false, false, false>(d, Ev, S.CC, a, S.ws, lane);
                 if (ok && lane < S.CC.nck) {
                     const int kk = S.CC.key[lane];
                     nch[kk] = S.ws.hdr[lane];
@@ -497,6 +595,8 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
                 __syncthreads();
             }
             write_back(id);
+            if constexpr (TOPO)
+                if (ctopo) topo_record<CT>(d, S.CC, S.ws, nch, ncw, E + id, tj, true, lane, -1, &P);
             if (lane == id) {
                 id_lc = c;
                 if (!pend) id_np++;
@@ -514,7 +614,7 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             uint64_t o = (lane < TW && d.tmpl_ok[j]) ? d.tmpl_opts[(size_t)j * TW + lane] : 0ull;
             o = sim_limit_filter(d, j, o, rem, lane);
             if (!ballot(o != 0)) continue;
-            if (S.CC.cls != c) fill_class_cache<false>(d, c, S.CC, lane, 64, 0ull);
+            if (S.CC.cls != c) fill_class_cache<TOPO>(d, c, S.CC, lane, 64, TOPO ? *P.born : 0ull);
             EvalIn a;
             a.Ahdr = d.cls_hdr + (size_t)(d.C + j) * K;
             a.Aw = d.cls_words + (size_t)(d.C + j) * DW;
@@ -525,10 +625,18 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             a.compat = true;
             a.force_off = false;
             a.prof = nullptr;
-            a.host = E + 1;
+            // a new NodeClaim's hostname: no pod counted there yet (TOPO: the next id's column; with 12 in flight it lies
+            // past the row and reads as empty)
+            a.host = TOPO ? E + n_nc : E + 1;
             a.held = 0;
             st_tmpl++;
-            if (!eval_wave<false, false, false>(d, Ev, S.CC, a, S.ws, lane)) continue;
+            if constexpr (TOPO) {
+                if (!(tcons ? eval_wave<true, false, false, true, CT>(d, Ev, S.CC, a, S.ws, lane)
+                            : eval_wave<false, false, false>(d, Ev, S.CC, a, S.ws, lane)))
+                    continue;
+            } else {
+                if (!eval_wave<false, false, false>(d, Ev, S.CC, a, S.ws, lane)) continue;
+            }
             if (n_nc >= KP_SIM_MAX_NODECLAIMS) {  // a thirteenth NodeClaim: the slice sort would no longer be insertionSort
                 overflow = true;
                 break;
@@ -566,6 +674,13 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
             }
             staged = id;
             write_back(id);
+            if constexpr (TOPO) {  // the NodeClaim's hostname column starts empty; Record the pod
+                for (int r = lane; r < k.HG; r += 64)
+                    __hip_atomic_store(&P.hd[(size_t)r * (E + KP_PT_SIM_COLS) + E + id], 0, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (ctopo) topo_record<CT>(d, S.CC, S.ws, nch, ncw, E + id, j, true, lane, -1, &P);
+            }
             if (lane == 0) d.nc_tmpl[ent_of(id)] = j;
             if (lane == id) {
                 id_tmpl = j;
@@ -623,8 +738,19 @@ __global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ 
     }
 }
 
+__global__ __launch_bounds__(64) void simulate_kernel(const KpDev* __restrict__ dp, const KpCons* __restrict__ kp,
+                                                      const KpSim* __restrict__ xp) {
+    simulate_body<false>(*dp, *kp, *xp);
+}
+// the same over a pass with topology groups (a ProbeTopo per worker)
+__global__ __launch_bounds__(64) void simulate_topo_kernel(const KpDev* __restrict__ dp, const KpCons* __restrict__ kp,
+                                                           const KpSim* __restrict__ xp) {
+    simulate_body<true>(*dp, *kp, *xp);
+}
+
 // Dynamic LDS of simulate_kernel: fixed block, the staged NodeClaim digest, limits, candidate / modified-node bitmaps.
-bool kp_sim_plan_lds(const KpDev& d, KpSim& x, int max_bytes) {
+// G > 0: a pass with topology groups (n_ha of them hostname pod affinities).
+bool kp_sim_plan_lds(const KpDev& d, KpSim& x, int max_bytes, int G, int n_ha) {
     auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
     size_t off = al(sizeof(SimShared));
     x.off_hdr = (int)off;
@@ -639,6 +765,17 @@ bool kp_sim_plan_lds(const KpDev& d, KpSim& x, int max_bytes) {
     off = al(off + 8 * (size_t)(d.EW > 0 ? d.EW : 1));
     x.off_mutn = (int)off;
     off = al(off + 8 * (size_t)(d.EW > 0 ? d.EW : 1));
+    x.off_touch = x.off_hmod = x.off_hpos = x.off_born = 0;
+    if (G > 0) {  // simulate_topo_kernel's ProbeTopo words
+        x.off_touch = (int)off;
+        off = al(off + 8 * (size_t)((G + 63) / 64));
+        x.off_hmod = (int)off;
+        off = al(off + 8 * (size_t)(d.EW > 0 ? d.EW : 1));
+        x.off_hpos = (int)off;
+        off = al(off + 4 * (size_t)(n_ha > 0 ? n_ha : 1));
+        x.off_born = (int)off;
+        off = al(off + 8);
+    }
     x.lds_bytes = (int)off;
     return (int)off <= max_bytes;
 }
@@ -646,9 +783,12 @@ bool kp_sim_plan_lds(const KpDev& d, KpSim& x, int max_bytes) {
 hipError_t kp_launch_simulate(const KpCons& k, const KpSim& x, hipStream_t s, const KpDev* d_dev, const KpCons* d_k,
                               const KpSim* d_x) {
     if (k.n_probes <= 0) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute((const void*)simulate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             KP_LDS_BYTES);
+    const void* fn = k.G > 0 ? (const void*)simulate_topo_kernel : (const void*)simulate_kernel;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(simulate_kernel, dim3(k.n_probes), dim3(64), (size_t)x.lds_bytes, s, d_dev, d_k, d_x);
+    if (k.G > 0)
+        hipLaunchKernelGGL(simulate_topo_kernel, dim3(k.n_probes), dim3(64), (size_t)x.lds_bytes, s, d_dev, d_k, d_x);
+    else
+        hipLaunchKernelGGL(simulate_kernel, dim3(k.n_probes), dim3(64), (size_t)x.lds_bytes, s, d_dev, d_k, d_x);
     return hipGetLastError();
 }

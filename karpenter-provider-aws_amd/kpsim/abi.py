@@ -304,7 +304,8 @@ assert LAUNCH_DTYPE.itemsize == C.sizeof(kp_launch_result)
 
 class kp_device_opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("n_devices", C.c_int32), ("devices", c_int32_p),
-                ("preference_policy", C.c_int32), ("reserved_capacity", C.c_int32)]
+                ("preference_policy", C.c_int32), ("reserved_capacity", C.c_int32),
+                ("simulate_topology", C.c_int32)]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -105,11 +105,13 @@ def load():
 class Context:
     """One kp_ctx (device stream + buffers).  Not thread-safe; use one per thread."""
 
-    def __init__(self, device=0, preference_policy=abi.KP_PREFERENCE_RESPECT, devices=None, reserved_capacity=1):
+    def __init__(self, device=0, preference_policy=abi.KP_PREFERENCE_RESPECT, devices=None, reserved_capacity=1,
+                 simulate_topology=0):
         L = load()
         self.L = L
         h = C.c_void_p()
-        opts = abi.kp_device_opts(device=device, preference_policy=preference_policy, reserved_capacity=reserved_capacity)
+        opts = abi.kp_device_opts(device=device, preference_policy=preference_policy, reserved_capacity=reserved_capacity,
+                                   simulate_topology=simulate_topology)
         if devices:
             import numpy as np
             self._devs = np.ascontiguousarray(devices, np.int32)
