@@ -413,7 +413,11 @@ kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out);
  * Profiling only: [50] candidate rounds made of such candidates alone, [51] rounds that mix them with evaluated ones
  * (n up to 52).  In the kernels that carry the bound (they have no topology section) [36] is not a cycle count: it
  * counts the in-flight commits that stored their NodeClaim's bound row again because an axis' largest type left the
- * options; the other in-flight commits left the row alone. */
+ * options; the other in-flight commits left the row alone.
+ * Profiling only, solves without topology groups: [52] the full pdqsort emulations of a slice longer than 64 NodeClaims
+ * (they start over LDS; kp_solve_stats.sorts_full minus these ran in registers from the start) and [53] their share of
+ * the cycles in [10] (n up to 54).  A solve with topology groups reports, in the same two places, the iterations that
+ * ended in a topology quick accept and their cycles. */
 kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n);
 
 /*

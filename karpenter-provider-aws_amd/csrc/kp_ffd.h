@@ -1148,7 +1148,7 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
             int pq[KP_LDS_AXES];
 #pragma unroll
             for (int ai = 0; ai < KP_LDS_AXES; ai++) pq[ai] = S.cur_pq[ai];
-            long long popped = S.st[ST_POPPED], scanned = 0, nquick = 0, sfast = 0, sfull = 0, csort = 0, csfull = 0;
+            long long popped = S.st[ST_POPPED], scanned = 0, nquick = 0, sfast = 0, sfull = 0, csort = 0, csfull = 0, sfull_w = 0, csfull_w = 0;
             long long cqpop = 0, cqscan = 0, cqcheck = 0, cqcommit = 0;
             long long n_noinv = 0, n_winmove = 0, n_ldssort = 0, n_pivot = 0, n_winload = 0, n_flush = 0, n_shape = 0;
             long long n_r2 = 0, n_rwb = 0, n_rout = 0, n_batch = 0, n_inner = 0, n_multi = 0, cqinner = 0;
@@ -1477,6 +1477,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                     const long long c1 = prof_clock(prof);
                     csort += c1 - t_b;
                     if (how == 2) csfull += c1 - t_b;
+                    if (PROF && how == 2 && N > 64) {  // the full sorts that start over LDS (ST_SORT_FULL_WIDE)
+                        sfull_w++;
+                        csfull_w += c1 - t_b;
+                    }
                     // positions < dpos are untouched by a stable move of dpos and rejected this shape (when the
                     // shape repeats); an append or a full pdqsort permutes everything
                     if (dkind == 2 || how == 2 || sstart > dpos) sstart = 0;
@@ -1824,6 +1828,10 @@ __device__ __forceinline__ void ffd_solve(KpDev d) {
                 if (PROF) {  // the diagnostic twin alone carries the stage cycles and the n_* counters
                     S.st[ST_CYC_SORT] += csort;
                     S.st[ST_CYC_SORT_FULL] += csfull;
+                    if (!TOPO_ON) {
+                        S.st[ST_SORT_FULL_WIDE] += sfull_w;
+                        S.st[ST_CYC_SORT_FULL_WIDE] += csfull_w;
+                    }
                     S.st[ST_CYC_QPOP] += cqpop;
                     S.st[ST_CYC_QSCAN] += cqscan;
                     S.st[ST_CYC_QCHECK] += cqcheck;

@@ -12,6 +12,7 @@
 // The stable move is a rotation of one run of equal keys, done by a whole wave.
 #pragma once
 #include "kp_device.h"
+#include "kp_gosort_core.h"
 
 // Slice keys carry the FFD rejection memo in bit 31 (the NodeClaim rejected the current pod shape); comparisons
 // use the low 31 bits = len(Pods).
@@ -31,19 +32,36 @@ struct SortSlice {
     }
 };
 
-__device__ __forceinline__ int go_bits_len(unsigned x) { return x ? 32 - __clz(x) : 0; }
+// A/B builds (DESIGN.md §6 "Full sorts: short ranges in registers").  KP_SORT_REG_RANGES 0: only a whole slice of
+// n <= 64 is sorted in registers and every sub-range of a longer one runs over LDS.  KP_SORT_PIVOT_LANES 0: choosePivot on
+// an LDS range compares its samples one dependent LDS round trip at a time (the generic go_choose_pivot).
+#ifndef KP_SORT_REG_RANGES
+#define KP_SORT_REG_RANGES 1
+#endif
+#ifndef KP_SORT_PIVOT_LANES
+#define KP_SORT_PIVOT_LANES 1
+#endif
+#ifndef KP_SORT_REG_SCANS
+#define KP_SORT_REG_SCANS 1  // 0: the register sorter walks partition / partitionEqual / partialInsertionSort one compare at a time
+#endif
 
-// The same slice held one element per lane (n <= 64): compares and swaps are readlanes on wave-uniform indices,
-// so the pdqsort emulation runs as scalar control flow without LDS round trips.
+// A range of the slice held one element per lane (index i lives in lane i - base, at most 64 of them): compares and
+// swaps are readlanes on wave-uniform indices, so the pdqsort emulation runs as scalar control flow without LDS round
+// trips.
 struct RegSlice {
     uint32_t k;
     uint32_t o;
     int lane;
+    int base;
+    static constexpr bool kRanges = false;
+    __device__ static __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
     __device__ __forceinline__ bool less(int i, int j) const {
-        return ((uint32_t)__builtin_amdgcn_readlane((int)k, i) & KEYMASK) <
-               ((uint32_t)__builtin_amdgcn_readlane((int)k, j) & KEYMASK);
+        return ((uint32_t)__builtin_amdgcn_readlane((int)k, i - base) & KEYMASK) <
+               ((uint32_t)__builtin_amdgcn_readlane((int)k, j - base) & KEYMASK);
     }
     __device__ __forceinline__ void swap(int i, int j) {
+        i -= base;
+        j -= base;
         const uint32_t ki = __builtin_amdgcn_readlane((int)k, i), kj = __builtin_amdgcn_readlane((int)k, j);
         const uint32_t oi = __builtin_amdgcn_readlane((int)o, i), oj = __builtin_amdgcn_readlane((int)o, j);
         if (lane == i) {
@@ -54,49 +72,37 @@ struct RegSlice {
             o = oi;
         }
     }
+    // scans (kp_gosort_core.h): one ballot over the lanes, no memory
+    __device__ __forceinline__ uint32_t key_at(int i) const { return (uint32_t)__builtin_amdgcn_readlane((int)k, i - base) & KEYMASK; }
+    template <class F>
+    __device__ __forceinline__ int find_first(int lo, int hi, F pred) const {
+        const int q = base + lane;
+        const uint64_t m = __ballot(q >= lo && q <= hi && pred(k & KEYMASK));
+        return m ? base + __ffsll((unsigned long long)m) - 1 : hi + 1;
+    }
+    template <class F>
+    __device__ __forceinline__ int find_last(int lo, int hi, F pred) const {
+        const int q = base + lane;
+        const uint64_t m = __ballot(q >= lo && q <= hi && pred(k & KEYMASK));
+        return m ? base + 63 - __clzll((long long)m) : lo - 1;
+    }
+    __device__ __forceinline__ int first_descent(int i, int b) const {
+        const uint32_t prev = (uint32_t)__shfl_up((int)k, 1) & KEYMASK;  // lane 0 is never asked (i > base)
+        const int q = base + lane;
+        const uint64_t m = __ballot(q >= i && q < b && lane > 0 && (k & KEYMASK) < prev);
+        return m ? base + __ffsll((unsigned long long)m) - 1 : b;
+    }
 };
-
-// order2_func / median_func / medianAdjacent_func / choosePivot_func (one lane)
-template <class D>
-__device__ inline void go_order2(const D& d, int a, int b, int& swaps, int& x, int& y) {
-    if (d.less(b, a)) {
-        swaps++;
-        x = b;
-        y = a;
-    } else {
-        x = a;
-        y = b;
-    }
+#if KP_SORT_REG_SCANS
+__device__ inline int go_partition(RegSlice& d, int a, int b, int pivot, bool& already) {
+    return go_partition_scans(d, a, b, pivot, already);
 }
-template <class D>
-__device__ inline int go_median(const D& d, int a, int b, int c, int& swaps) {
-    int x, y;
-    go_order2(d, a, b, swaps, x, y);
-    a = x;
-    b = y;
-    go_order2(d, b, c, swaps, x, y);
-    b = x;
-    c = y;
-    go_order2(d, a, b, swaps, x, y);
-    return y;
+__device__ inline int go_partition_equal(RegSlice& d, int a, int b, int pivot) {
+    return go_partition_equal_scans(d, a, b, pivot);
 }
-// hint: 0 unknown, 1 increasing, 2 decreasing
-template <class D>
-__device__ inline void go_choose_pivot(const D& d, int a, int b, int& pivot, int& hint) {
-    const int l = b - a;
-    int swaps = 0;
-    int i = a + l / 4 * 1, j = a + l / 4 * 2, k = a + l / 4 * 3;
-    if (l >= 8) {
-        if (l >= 50) {
-            i = go_median(d, i - 1, i, i + 1, swaps);
-            j = go_median(d, j - 1, j, j + 1, swaps);
-            k = go_median(d, k - 1, k, k + 1, swaps);
-        }
-        j = go_median(d, i, j, k, swaps);
-    }
-    pivot = j;
-    hint = swaps == 0 ? 1 : (swaps == 12 ? 2 : 0);
-}
+__device__ inline bool go_partial_insertion_sort(RegSlice& d, int a, int b) { return go_partial_insertion_sort_scans(d, a, b); }
+__device__ inline void go_insertion_sort(RegSlice& d, int a, int b) { go_insertion_sort_scans(d, a, b); }
+#endif
 
 // Same swaps count as go_choose_pivot(0, n) but with the ≤ 9 sampled keys loaded by lanes in parallel.
 __device__ inline int choose_pivot_hint_wave(const SortSlice& d, int n, int lane) {
@@ -133,187 +139,6 @@ __device__ inline int choose_pivot_hint_wave(const SortSlice& d, int n, int lane
         med(v[0], v[1], v[2]);
     }
     return swaps == 0 ? 1 : (swaps == 12 ? 2 : 0);
-}
-
-template <class D>
-__device__ inline void go_insertion_sort(D& d, int a, int b) {
-    for (int i = a + 1; i < b; i++)
-        for (int j = i; j > a && d.less(j, j - 1); j--) d.swap(j, j - 1);
-}
-template <class D>
-__device__ inline void go_sift_down(D& d, int lo, int hi, int first) {
-    int root = lo;
-    for (;;) {
-        int child = 2 * root + 1;
-        if (child >= hi) return;
-        if (child + 1 < hi && d.less(first + child, first + child + 1)) child++;
-        if (!d.less(first + root, first + child)) return;
-        d.swap(first + root, first + child);
-        root = child;
-    }
-}
-template <class D>
-__device__ inline void go_heap_sort(D& d, int a, int b) {
-    const int first = a, lo = 0, hi = b - a;
-    for (int i = (hi - 1) / 2; i >= 0; i--) go_sift_down(d, i, hi, first);
-    for (int i = hi - 1; i >= 0; i--) {
-        d.swap(first, first + i);
-        go_sift_down(d, lo, i, first);
-    }
-}
-template <class D>
-__device__ inline int go_partition(D& d, int a, int b, int pivot, bool& already) {
-    d.swap(a, pivot);
-    int i = a + 1, j = b - 1;
-    while (i <= j && d.less(i, a)) i++;
-    while (i <= j && !d.less(j, a)) j--;
-    if (i > j) {
-        d.swap(j, a);
-        already = true;
-        return j;
-    }
-    d.swap(i, j);
-    i++;
-    j--;
-    for (;;) {
-        while (i <= j && d.less(i, a)) i++;
-        while (i <= j && !d.less(j, a)) j--;
-        if (i > j) break;
-        d.swap(i, j);
-        i++;
-        j--;
-    }
-    d.swap(j, a);
-    already = false;
-    return j;
-}
-template <class D>
-__device__ inline int go_partition_equal(D& d, int a, int b, int pivot) {
-    d.swap(a, pivot);
-    int i = a + 1, j = b - 1;
-    for (;;) {
-        while (i <= j && !d.less(a, i)) i++;
-        while (i <= j && d.less(a, j)) j--;
-        if (i > j) break;
-        d.swap(i, j);
-        i++;
-        j--;
-    }
-    return i;
-}
-template <class D>
-__device__ inline bool go_partial_insertion_sort(D& d, int a, int b) {
-    int i = a + 1;
-    for (int j = 0; j < 5; j++) {
-        while (i < b && !d.less(i, i - 1)) i++;
-        if (i == b) return true;
-        if (b - a < 50) return false;
-        d.swap(i, i - 1);
-        if (i - a >= 2) {
-            for (int k = i - 1; k >= 1; k--) {  // Go bounds this loop by 1, not a
-                if (!d.less(k, k - 1)) break;
-                d.swap(k, k - 1);
-            }
-        }
-        if (b - i >= 2) {
-            for (int k = i + 1; k < b; k++) {
-                if (!d.less(k, k - 1)) break;
-                d.swap(k, k - 1);
-            }
-        }
-    }
-    return false;
-}
-template <class D>
-__device__ inline void go_break_patterns(D& d, int a, int b) {
-    const int length = b - a;
-    if (length >= 8) {
-        uint64_t random = (uint64_t)length;  // xorshift(length)
-        const uint64_t modulus = 1ull << go_bits_len((unsigned)length);
-        const int idx = a + (length / 4) * 2 - 1;
-        for (int i = 0; i < 3; i++) {
-            random ^= random << 13;
-            random ^= random >> 7;
-            random ^= random << 17;
-            int other = (int)(random & (modulus - 1));
-            if (other >= length) other -= length;
-            d.swap(idx - 1 + i, a + other);
-        }
-    }
-}
-template <class D>
-__device__ inline void go_reverse_range(D& d, int a, int b) {
-    int i = a, j = b - 1;
-    while (i < j) {
-        d.swap(i, j);
-        i++;
-        j--;
-    }
-}
-// pdqsort_func(data, 0, n, bits.Len(n)) with Go's recursion order (smaller side first) on an explicit stack.
-template <class D>
-__device__ inline void pdqsort_full(D& d, int n, int* stk) {
-    int sp = 0;
-    auto push = [&](int a, int b, int limit, int wb, int wp) {
-        stk[sp * 5 + 0] = a;
-        stk[sp * 5 + 1] = b;
-        stk[sp * 5 + 2] = limit;
-        stk[sp * 5 + 3] = wb;
-        stk[sp * 5 + 4] = wp;
-        sp++;
-    };
-    push(0, n, go_bits_len((unsigned)n), 1, 1);
-    while (sp > 0) {
-        sp--;
-        int a = __builtin_amdgcn_readfirstlane(stk[sp * 5 + 0]), b = __builtin_amdgcn_readfirstlane(stk[sp * 5 + 1]);
-        int limit = __builtin_amdgcn_readfirstlane(stk[sp * 5 + 2]);
-        bool wasBalanced = __builtin_amdgcn_readfirstlane(stk[sp * 5 + 3]) != 0;
-        bool wasPartitioned = __builtin_amdgcn_readfirstlane(stk[sp * 5 + 4]) != 0;
-        for (;;) {
-            const int length = b - a;
-            if (length <= 12) {
-                go_insertion_sort(d, a, b);
-                break;
-            }
-            if (limit == 0) {
-                go_heap_sort(d, a, b);
-                break;
-            }
-            if (!wasBalanced) {
-                go_break_patterns(d, a, b);
-                limit--;
-            }
-            int pivot, hint;
-            go_choose_pivot(d, a, b, pivot, hint);
-            if (hint == 2) {
-                go_reverse_range(d, a, b);
-                pivot = (b - 1) - (pivot - a);
-                hint = 1;
-            }
-            if (wasBalanced && wasPartitioned && hint == 1) {
-                if (go_partial_insertion_sort(d, a, b)) break;
-            }
-            if (a > 0 && !d.less(a - 1, pivot)) {
-                a = go_partition_equal(d, a, b, pivot);
-                continue;
-            }
-            bool already = false;
-            const int mid = go_partition(d, a, b, pivot, already);
-            wasPartitioned = already;
-            const int leftLen = mid - a, rightLen = b - mid;
-            const int balanceThreshold = length / 8;
-            if (leftLen < rightLen) {
-                wasBalanced = leftLen >= balanceThreshold;
-                push(mid + 1, b, limit, wasBalanced, wasPartitioned);  // the loop continues here afterwards
-                push(a, mid, limit, 1, 1);                             // recursive pdqsort_func first
-            } else {
-                wasBalanced = rightLen >= balanceThreshold;
-                push(a, mid, limit, wasBalanced, wasPartitioned);
-                push(mid + 1, b, limit, 1, 1);
-            }
-            break;
-        }
-    }
 }
 
 // ---- wave-parallel pieces of the stable move ----
@@ -391,6 +216,31 @@ struct WaveLds {
     uint32_t* key;
     uint16_t* ord;
     int lane;
+    static constexpr bool kRanges = KP_SORT_REG_RANGES != 0;
+    __device__ static __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+    // A popped range that fits the lanes with its predecessor ([a-1, b), or [0, b) when a == 0, at most 64 elements) is
+    // finished in registers with all its descendants: one LDS round trip in, the RegSlice sorter from the popped entry
+    // with the stack continuing at sp, one round trip out (kp_gosort_core.h gives the argument for exactness).  Lane 0
+    // holds the read-only predecessor and does not write back.  A whole slice of n <= 64 arrives here as the root entry
+    // (0, n), so the kernel holds one instantiation of the register sorter, at this one call site.
+    __device__ inline bool hand_over(int a, int b, int limit, bool wb, bool wp, int* stk, int sp) {
+        const int base = a > 0 ? a - 1 : 0;
+        if (b - base > 64) return false;
+        if (b - a < 2) return true;  // insertionSort of at most one element: no compare, no swap
+        RegSlice r;
+        r.lane = lane;
+        r.base = base;
+        const int p = base + lane;
+        r.k = p < b ? key[p] : 0u;
+        r.o = p < b ? ord[p] : 0u;
+        pdqsort_from(r, stk, sp, a, b, limit, wb, wp);
+        if (p >= a && p < b) {
+            key[p] = r.k;
+            ord[p] = (uint16_t)r.o;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        return true;
+    }
     __device__ __forceinline__ uint32_t k(int i) const { return (uint32_t)__builtin_amdgcn_readfirstlane((int)key[i]) & KEYMASK; }
     __device__ __forceinline__ bool less(int i, int j) const { return k(i) < k(j); }
     __device__ __forceinline__ void swap(int i, int j) {
@@ -478,6 +328,22 @@ struct WaveLds {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
 };
+
+#if KP_SORT_PIVOT_LANES
+// choosePivot_func of an LDS range in one round trip: lanes load the 9 (or 3) sampled keys, one readlane each brings
+// them to SGPRs, and go_choose_pivot_vals runs Go's network on (value, index) pairs.
+__device__ inline void go_choose_pivot(const WaveLds& d, int a, int b, int& pivot, int& hint) {
+    const int l = b - a;
+    uint32_t v[9] = {};
+    if (l >= 8) {
+        const int nl = l >= 50 ? 9 : 3;
+        const uint32_t kv = d.lane < nl ? (d.key[go_pivot_sample_pos(a, b, d.lane)] & KEYMASK) : 0u;
+#pragma unroll
+        for (int q = 0; q < 9; q++) v[q] = __builtin_amdgcn_readlane(kv, q);
+    }
+    go_choose_pivot_vals(v, a, b, pivot, hint);
+}
+#endif
 
 // partition_func with wave scans
 __device__ inline int go_partition(WaveLds& d, int a, int b, int pivot, bool& already) {
@@ -582,11 +448,14 @@ __device__ inline void go_reverse_range(WaveLds& d, int a, int b) {
     }
 }
 
-// Full pdqsort_func emulation: in registers for n <= 64, else on lane 0 over LDS.
+// Full pdqsort_func emulation: over LDS while a range is longer than the lanes hold, in registers from there down
+// (WaveLds::hand_over; a slice of n <= 64 is such a range from the start).
 __device__ inline void pdqsort_any(SortSlice d, int n, int* stk, int lane) {
+#if !KP_SORT_REG_RANGES
     if (n <= 64) {
         RegSlice r;
         r.lane = lane;
+        r.base = 0;
         r.k = lane < n ? d.key[lane] : 0u;
         r.o = lane < n ? d.ord[lane] : 0u;
         pdqsort_full(r, n, stk);
@@ -596,6 +465,7 @@ __device__ inline void pdqsort_any(SortSlice d, int n, int* stk, int lane) {
         }
         return;
     }
+#endif
     WaveLds w{d.key, d.ord, lane};
     pdqsort_full(w, n, stk);
 }

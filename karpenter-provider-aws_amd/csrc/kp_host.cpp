@@ -435,7 +435,7 @@ struct kp_ctx {
     double ns_prep = 0, ns_exec = 0, ns_fin = 0;
     hipEvent_t ev[6] = {};
     double kernel_ms[5] = {};
-    int64_t cycles[47] = {};  // FFD phases (s_memtime): pop, sort, scan+eval, templates, commit, full pdqsort
+    int64_t cycles[49] = {};  // FFD phases (s_memtime): pop, sort, scan+eval, templates, commit, full pdqsort
     bool any_min_values = false;             // some template requirement carries minValues
     int max_min_values = 0;                  // the largest minValues among the template requirements
     bool min_multi = false;                  // ... on a multi-valued catalog key (zone, capacity type, ...)
@@ -3839,6 +3839,8 @@ extern "C" kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out) {
     c->cycles[44] = st[ST_BOUND_SKIPS];
     c->cycles[45] = st[ST_BOUND_ALLV];
     c->cycles[46] = st[ST_BOUND_MIXED];
+    c->cycles[47] = st[ST_SORT_FULL_WIDE];
+    c->cycles[48] = st[ST_CYC_SORT_FULL_WIDE];
     if (getenv("KPSIM_PROFILE") && st[ST_SLOW_WHY] + st[ST_SLOW_WHY + 1] + st[ST_SLOW_WHY + 2] + st[ST_SLOW_WHY + 3])
         fprintf(stderr, "[kpsim] slow-path pods: no candidate %lld, class not absorbed %lld, witness short %lld, no witness table %lld; "
                 "no-op merge quick accepts %lld; placed by the first candidate %lld, a later one %lld, the templates %lld; "
@@ -3890,7 +3892,7 @@ extern "C" kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n) {
     if (!ctx || !ms) return KP_E_INVALID;
     if (!ctx->executed) return fail(ctx, KP_E_STATE, "no execute yet");
     for (int i = 0; i < n && i < 5; i++) ms[i] = ctx->kernel_ms[i];
-    for (int i = 5; i < n && i < 52; i++) ms[i] = (double)ctx->cycles[i - 5];
+    for (int i = 5; i < n && i < 54; i++) ms[i] = (double)ctx->cycles[i - 5];
     return KP_OK;
 }
 

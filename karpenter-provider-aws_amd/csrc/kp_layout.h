@@ -386,6 +386,10 @@ enum {
     // options, kp_bound.h); the others left it alone.  It shares the slot of ST_CYC_TSETUP: the kernels that carry the
     // bound have no topology section, and the topology kernels carry no bound (kp_last_kernel_times [36])
     ST_BOUND_ROWS = 46,
+    // KPSIM_PROFILE: the full pdqsort emulations of a slice longer than 64 (they start over LDS; the others run in registers
+    // from the start) and their share of ST_CYC_SORT_FULL.  They share the slots of ST_TQ_ITERS / ST_TQ_CYC: the kernels of
+    // a solve with topology groups write those and leave the split out (kp_last_kernel_times [52..53])
+    ST_SORT_FULL_WIDE = 75, ST_CYC_SORT_FULL_WIDE = 76,
     ST_EV_REQ = 16, ST_EV_MASK, ST_EV_OFF, ST_EV_TYPES, ST_EV_MIN, ST_EV_CALLS,
     ST_QUICK = 24, ST_SLOW, ST_WITNESS_MISS, ST_CYC_QPOP, ST_CYC_QSCAN, ST_CYC_QCHECK, ST_CYC_QCOMMIT,
     ST_N_NOINV = 32, ST_N_WINMOVE, ST_N_LDSSORT, ST_N_PIVOT, ST_N_WINLOAD, ST_N_FLUSH, ST_N_SHAPE, ST_EXIST_PLACED = 44,
@@ -406,6 +410,7 @@ enum {
     ST_HANDOFF = 77, ST_HANDOFF_WB = 43, ST_COUNT = 80
 };
 static_assert(ST_BOUND_ROWS == ST_CYC_TSETUP, "ST_BOUND_ROWS shares the topology setup slot");
+static_assert(ST_SORT_FULL_WIDE == ST_TQ_ITERS && ST_CYC_SORT_FULL_WIDE == ST_TQ_CYC, "the full-sort split shares the topology quick-accept slots");
 // The stage cycles (ST_CYC_*, ST_EV_REQ .. ST_EV_MIN, ST_SEG, ST_TQ_CYC, ST_HANDOFF), the ST_N_* counters and the
 // ST_TQ_WHY / ST_SLOW_WHY breakdowns are written by the diagnostic twins of the Solve kernels alone (ffd_solve PROF) and
 // read 0 otherwise; every other slot is exact in both.

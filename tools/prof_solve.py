@@ -24,7 +24,10 @@ NAMES = ["cyc_fast_loop", "cyc_sort", "cyc_slow_eval", "cyc_templates", "-", "cy
          "n_inner", "cyc_q_inner", "n_multi",
          # slow-path candidates the headroom bound rejected without an evaluation (kp_layout.h ST_BOUND_SKIPS, always
          # exact), the candidate rounds made of them alone and the rounds that mix them with evaluated candidates
-         "bound_skips", "rounds_all_virtual", "rounds_mixed"]
+         "bound_skips", "rounds_all_virtual", "rounds_mixed",
+         # the full pdqsort emulations of a slice longer than 64 (they start over LDS) and their share of cyc_sort_full
+         # (kp_layout.h ST_SORT_FULL_WIDE; a solve with topology groups reports its topology quick-accept iterations here)
+         "sorts_full_n_gt_64", "cyc_sort_full_n_gt_64"]
 
 
 def ffd_counters(ctx):
@@ -59,6 +62,9 @@ def main():
     # in-flight commits that stored their NodeClaim's bound row again (kp_layout.h ST_BOUND_ROWS, kpsim.h [36])
     if which == "config2":
         ffd["bound_rows_stored"] = ffd.pop("cyc_topo_setup")
+    # the split of the full sorts: the ones of at most 64 elements run in registers from the start
+    ffd["sorts_full_n_le_64"] = r.stats["sorts_full"] - ffd["sorts_full_n_gt_64"]
+    ffd["cyc_sort_full_n_le_64"] = ffd["cyc_sort_full"] - ffd["cyc_sort_full_n_gt_64"]
     print(json.dumps({"config": which, "pods": n, "wall_ms": wall, "kernel_ms": kt, "nodeclaims": r.n_nodeclaims, "stats": r.stats,
                       "ffd": ffd}, indent=1))
     ctx.close()
