@@ -420,6 +420,18 @@ kp_status kp_solve_fetch(kp_ctx* ctx, kp_solve_output* out);
  * ended in a topology quick accept and their cycles. */
 kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n);
 
+/* Diagnostics: the plan of the last kp_solve_execute (read-only; tests and tools tell by it which Solve entry point and
+ * LDS layout a solve ran with).  Copies min(n, KP_SOLVE_PLAN_N) values: [0] the in-flight NodeClaim capacity the prepare
+ * planned (4096 or the prepare's node-dense estimate for a first plan, never more than the pod count; the pod count,
+ * capped at 65,535, for the one re-plan after "in-flight NodeClaim capacity exceeded"), [1] the kernel's NodeClaim
+ * slots, [2] NodeClaims with a quick-accept headroom row (ids below it), [3] quick-accept axes, [4] 1 = the allocatable
+ * table is read from HBM, not staged in LDS, [5] 1 = the slice arrays are in HBM, [6] 1 = the reserved-offering rows
+ * are staged in LDS; the features that selected the entry point: [7] node-side state (host ports, volume limits),
+ * [8] preference relaxation or BestEffort minValues, [9] reserved offerings, [10] topology groups, [11] 1 = the
+ * diagnostic build (KPSIM_PROFILE / KPSIM_TRACE_POD); [12] dynamic LDS bytes.  KP_E_STATE before the first execute. */
+#define KP_SOLVE_PLAN_N 13
+kp_status kp_last_solve_plan(kp_ctx* ctx, int32_t* out, int32_t n);
+
 /*
  * Diagnostics: the volume encoding of the prepared Solve or consolidation pass (what kp_solve_prepare /
  * kp_consolidate_prepare derived from the volume tables), copied into buf as int64 values; *needed receives the

@@ -3896,6 +3896,17 @@ extern "C" kp_status kp_last_kernel_times(kp_ctx* ctx, double* ms, int32_t n) {
     return KP_OK;
 }
 
+extern "C" kp_status kp_last_solve_plan(kp_ctx* ctx, int32_t* out, int32_t n) {
+    if (!ctx || !out) return KP_E_INVALID;
+    if (!ctx->executed) return fail(ctx, KP_E_STATE, "no execute yet");
+    const KpDev& d = ctx->dev;
+    const KpFfdPick k = kp_ffd_pick(d);  // the expression kp_launch_ffd picked the entry point by
+    const int32_t v[KP_SOLVE_PLAN_N] = {d.NCcap, d.lds_ncmax, d.lds_nq,  d.lds_A, d.alloc_global, d.slice_hbm, d.ro_stage,
+                                        k.ports, k.pref,      k.resv,    k.topo,  k.twin,         d.lds_bytes};
+    for (int i = 0; i < n && i < KP_SOLVE_PLAN_N; i++) out[i] = v[i];
+    return KP_OK;
+}
+
 extern "C" kp_status kp_solve(kp_ctx* ctx, const kp_solve_input* in, kp_solve_output* out) {
     for (int attempt = 0;; attempt++) {
         kp_status st = kp_solve_prepare(ctx, in);

@@ -496,13 +496,12 @@ hipError_t kp_launch_ffd(const KpDev& d, hipStream_t s) {
     // instantiation by solve features: reserved offerings (RESV), topology groups (TOPO), preference relaxation or
     // BestEffort minValues (PREF)
     const dim3 g(1), b((d.G > 0 ? KP_NWAVES_TOPO : KP_NWAVES) * 64);
-    const bool pref = d.relax_next || d.best_effort;
-    // KPSIM_PROFILE / KPSIM_TRACE_POD: the diagnostic twin (the production kernels carry no stamps, n_* counters or trace)
-    const int twin = (d.profile || d.trace) ? 1 : 0;
-    // a solve with node-side state beyond requests (host ports, PW > 0; volume limits, VD > 0) runs the PORTS
-    // instantiations; every other solve the entry point it always had
-    const FfdKernel k = (d.PW > 0 || d.VD > 0) ? kFfdPortsKernels[twin][(d.slice_hbm ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)]
-                                 : kFfdKernels[twin][(d.slice_hbm ? 8 : 0) + (pref ? 4 : 0) + (d.ro ? 2 : 0) + (d.G > 0 ? 1 : 0)];
+    // KPSIM_PROFILE / KPSIM_TRACE_POD: the diagnostic twin (the production kernels carry no stamps, n_* counters or trace).
+    // A solve with node-side state beyond requests (host ports, PW > 0; volume limits, VD > 0) runs the PORTS
+    // instantiations; every other solve the entry point it always had (kp_ffd_pick, kp_layout.h: the same bits that
+    // kp_last_solve_plan reports)
+    const KpFfdPick pick = kp_ffd_pick(d);
+    const FfdKernel k = pick.ports ? kFfdPortsKernels[pick.twin][pick.index()] : kFfdKernels[pick.twin][pick.index()];
     hipLaunchKernelGGL(k, g, b, bytes, s, d);
     return hipGetLastError();
 }

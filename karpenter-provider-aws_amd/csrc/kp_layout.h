@@ -368,6 +368,27 @@ struct KpDev {
     const uint8_t* ex_vover;         // [E] the node is over a limit at prepare: ExistingNode.Add fails for every pod
 };
 
+// The Solve entry point of a planned KpDev, by feature: what kp_launch_ffd (kp_kernels.hip) indexes its tables with and
+// what kp_last_solve_plan (kp_host.cpp) reports, from one expression.  ports: node-side state beyond requests (host
+// ports, volume limits), whose instantiations carry PREF; pref: preference relaxation or BestEffort minValues; resv:
+// reserved offerings; topo: topology groups; hbm: the slice arrays in HBM; twin: the diagnostic build (KPSIM_PROFILE /
+// KPSIM_TRACE_POD).
+struct KpFfdPick {
+    int ports, pref, resv, topo, hbm, twin;
+    // kFfdPortsKernels[twin][HBM * 4 + RESV * 2 + TOPO] with ports, else kFfdKernels[twin][HBM * 8 + PREF * 4 + RESV * 2 + TOPO]
+    int index() const { return ports ? hbm * 4 + resv * 2 + topo : hbm * 8 + pref * 4 + resv * 2 + topo; }
+};
+static inline KpFfdPick kp_ffd_pick(const KpDev& d) {
+    KpFfdPick k;
+    k.ports = (d.PW > 0 || d.VD > 0) ? 1 : 0;
+    k.pref = (d.relax_next || d.best_effort) ? 1 : 0;
+    k.resv = d.ro ? 1 : 0;
+    k.topo = d.G > 0 ? 1 : 0;
+    k.hbm = d.slice_hbm ? 1 : 0;
+    k.twin = (d.profile || d.trace) ? 1 : 0;
+    return k;
+}
+
 // stats slots
 enum {
     ST_POPPED = 0, ST_NC_EVALS, ST_NC_SCANNED, ST_TMPL_EVALS, ST_EXIST_EVALS, ST_SORT_FAST, ST_SORT_FULL,

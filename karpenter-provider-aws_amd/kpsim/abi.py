@@ -158,6 +158,11 @@ class kp_solve_output(C.Structure):
                 ("pod_order", c_int32_p), ("stats", kp_solve_stats)]
 
 
+# kp_last_solve_plan (kpsim.h): the values in order (KP_SOLVE_PLAN_N of them)
+SOLVE_PLAN_FIELDS = ("NCcap", "lds_ncmax", "lds_nq", "lds_A", "alloc_global", "slice_hbm", "ro_stage",
+                     "ports", "pref", "resv", "topo", "twin", "lds_bytes")
+
+
 KP_CONSOLIDATE_SINGLE, KP_CONSOLIDATE_MULTI, KP_CONSOLIDATE_BOTH = 0, 1, 2
 KP_DECISION_NONE, KP_DECISION_DELETE, KP_DECISION_REPLACE = 0, 1, 2
 KP_CT_ON_DEMAND, KP_CT_SPOT, KP_CT_RESERVED = 0, 1, 2

@@ -10,10 +10,11 @@ LIB_PATH = os.path.join(PKG_DIR, "..", "lib", "libkpsim.so")
 EXPORTS = [
     "kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_version", "kp_catalog_upload", "kp_catalog_patch_avail",
     "kp_catalog_patch_price", "kp_solve", "kp_solve_prepare", "kp_solve_execute", "kp_solve_fetch",
-    "kp_result_nodeclaim_requirements", "kp_last_kernel_times", "kp_consolidate_probe_count", "kp_consolidate",
-    "kp_consolidate_stats", "kp_consolidate_prepare", "kp_consolidate_execute", "kp_launch_select", "kp_launch_stats",
-    "kp_nodeclaim_labels", "kp_catalog_build", "kp_catalog_get_view", "kp_catalog_overhead", "kp_catalog_resource_name",
-    "kp_catalog_free", "kp_consolidate_command", "kp_consolidate_replacement", "kp_solve_volume_encoding",
+    "kp_result_nodeclaim_requirements", "kp_last_kernel_times", "kp_last_solve_plan", "kp_consolidate_probe_count",
+    "kp_consolidate", "kp_consolidate_stats", "kp_consolidate_prepare", "kp_consolidate_execute", "kp_launch_select",
+    "kp_launch_stats", "kp_nodeclaim_labels", "kp_catalog_build", "kp_catalog_get_view", "kp_catalog_overhead",
+    "kp_catalog_resource_name", "kp_catalog_free", "kp_consolidate_command", "kp_consolidate_replacement",
+    "kp_solve_volume_encoding",
     "kp_solve_explain", "kp_solve_explain_key", "kp_solve_explain_stats", "kp_consolidate_explain",
     "kp_consolidate_explain_pods", "kp_consolidate_explain_key", "kp_consolidate_explain_stats",
     "kp_simulate_execute", "kp_simulate_nodeclaims", "kp_simulate_nodeclaim_requirements", "kp_drift_command",
@@ -60,6 +61,8 @@ def load():
     L.kp_solve_fetch.argtypes = [C.c_void_p, C.POINTER(abi.kp_solve_output)]
     L.kp_result_nodeclaim_requirements.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
     L.kp_last_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
+    if hasattr(L, "kp_last_solve_plan"):  # (absent from older libraries, A/B only)
+        L.kp_last_solve_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.kp_consolidate_probe_count.argtypes = [C.POINTER(abi.kp_consolidate_input)]
     L.kp_consolidate.argtypes = [C.c_void_p, C.POINTER(abi.kp_consolidate_input), C.POINTER(abi.kp_probe_result),
                                  C.c_int32]
@@ -277,6 +280,13 @@ class Context:
         a = (C.c_double * 42)()
         self.check(self.L.kp_last_kernel_times(self.h, a, 42), "kp_last_kernel_times")
         return list(a)[5:]
+
+    def solve_plan(self):
+        """kp_last_solve_plan of the last execute as a dict (abi.SOLVE_PLAN_FIELDS): the planned NodeClaim capacity and
+        LDS layout, and the feature bits that selected the Solve entry point.  Diagnostics."""
+        a = (C.c_int32 * len(abi.SOLVE_PLAN_FIELDS))()
+        self.check(self.L.kp_last_solve_plan(self.h, a, len(a)), "kp_last_solve_plan")
+        return dict(zip(abi.SOLVE_PLAN_FIELDS, (int(x) for x in a)))
 
     def consolidate(self, cons_view):
         """kp_consolidate over the view's probe range -> numpy array of abi.PROBE_DTYPE (one row per probe)."""

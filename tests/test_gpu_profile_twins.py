@@ -5,8 +5,9 @@ always-on counters; the stage cycles and n_* counters are written by the twin al
 kernel.  Each problem reaches the block path and the templates (asserted on the oracle's result and the device's
 slow-path count).
 
-The *_hbm_kernel twins are not covered: the slice arrays move to HBM only for solves planned for more NodeClaims than
-LDS holds, which no problem of a few hundred pods reaches."""
+The *_hbm_kernel twins run in tests/test_gpu_dense_plans.py (test_dense_twin: base and topology at 18,100 pods): the
+slice arrays move to HBM only for solves planned for more NodeClaims than LDS holds, which no problem of a few hundred
+pods reaches."""
 import ctypes as C
 import os
 
@@ -78,14 +79,16 @@ def _counters(ctx):
     return dict(zip(NAMES, list(a)[5:]))
 
 
-def _solve(prob, policy, profile):
+def _solve(prob, policy, profile, want_plan=False):
+    """(result, counters) of one solve on a fresh ctx, KPSIM_PROFILE set or unset at prepare; want_plan: and the plan
+    of the solve (Context.solve_plan)"""
     old = os.environ.pop("KPSIM_PROFILE", None)
     if profile:
         os.environ["KPSIM_PROFILE"] = "1"
     ctx = native.Context(0, preference_policy=policy)
     try:
         dev = parity.run_device(ctx, prob)
-        return dev, _counters(ctx)
+        return (dev, _counters(ctx), ctx.solve_plan()) if want_plan else (dev, _counters(ctx))
     finally:
         ctx.close()
         os.environ.pop("KPSIM_PROFILE", None)
